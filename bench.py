@@ -10,8 +10,19 @@ ComputeGreedyPCA -> ComputeTGLR dense parts) over one synthetic (Nz, N, N) cube 
 inputs (raw, var, mask) are already resident in HBM.  With N > 1 ranks the field is cut into
 spatial tiles (one per GPU, PCA areas never straddle tiles) and the total work is fixed
 (strong scaling).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`).  Everything else the line can hold -- the oracle check, the CPU baseline, the
+PCIe-inclusive pass, the runs without the local maxima and in the sequential form, the per-kernel
+tables, the roofline blocks and the per-rank table -- comes with --full.
+
+--dump-outputs DIR (one rank only) writes what the last timed step computed, right after the
+timed steps, as DIR/<name>.npy: the 2-D maps whole (up to 1024 x 1024 spaxels), the per-area
+thresholds, and of every cube the same fixed, seeded sample of voxels as a flat float32 vector
+(DIR/sample_index.npy: their linear indices in the (Nz, N, N) cube, float64).
 """
 import argparse
+import ctypes as C
 import json
 import multiprocessing as mp
 import os
@@ -82,6 +93,132 @@ def _gen_chunk(args):
 _gen_chunk.cache = {}
 
 
+METRIC = "voxels/s through DCT+PCA+GLR (ORIGIN hot path)"
+
+
+def step_text(args, sparse_lm):
+    return ("Preprocessing (DCT, standardise) -> PCA thresholds -> greedy PCA -> TGLR "
+            "(correl, correl_min, profile, maxmap, minmap" +
+            (", cube_local_max, cube_local_min" + (" as lists of their non-zero voxels)"
+                                                   if sparse_lm else ")")
+             if args.local_max else ")"))
+
+
+def dtype_text(glr_precision):
+    return "f32" if glr_precision == "f32" else f"f32+{glr_precision}"
+
+
+def spread(step_ms):
+    return {"min": round(min(step_ms), 3), "median": round(float(np.median(step_ms)), 3),
+            "max": round(max(step_ms), 3), "n": len(step_ms),
+            "note": "wall time of each timed step on this rank (every step ends with a "
+                    "synchronisation)"}
+
+
+def config_block(args, Nz, N, glr_precision, world, comm, info, t_gen):
+    return {"workload": f"synthetic {Nz}x{N}x{N} cube, Dico_FWHM_2_12 "
+                        f"({args.nprof} profiles), PSF 25x25, 100x100 areas, "
+                        "dct_order 10, pfa 0.01, Noise_population 50, itermax 100",
+            "arithmetic": "DCT/PCA: f32 storage, f64 reductions and eigen-solve; GLR: "
+                          + {"f16x2": "two-term f16 split on the matrix cores, fp32 "
+                                      "accumulate (fp32-class: 22 significant bits)",
+                             "bf16": "single bf16 MFMA per product, fp32 accumulate",
+                             "f32": "fp32 FMA"}.get(glr_precision, glr_precision),
+            "masked_border": args.masked_border,
+            "glr_spectral_arithmetic": glr_precision, "tiles": world,
+            "comm": (comm.backend + (" " + comm.note if comm.note else ""))
+            if comm is not None else None, "pca": info,
+            "gen_seconds": round(t_gen, 1)}
+
+
+def close_all(comm, plans, ctx):
+    if comm is not None:
+        comm.close()
+    # plans and the context go before the interpreter does (origin_amd.device closes contexts at
+    # exit anyway; a context left to the HIP runtime's static destructors aborts the process)
+    for obj in plans:
+        try:
+            obj.close()
+        except Exception:
+            pass
+    ctx.close()
+
+
+# --dump-outputs: a fixed sample of every cube -- DUMP_BOXES boxes of 4 x 4 spaxels over (at most)
+# DUMP_MAX_NZ channels, and DUMP_PLANES single channels of (at most) 128 x 128 spaxels, at places
+# drawn from DUMP_SEED and the cube's shape only -- and the 2-D maps up to 1024 x 1024
+DUMP_SEED = 20261016
+DUMP_BOXES, DUMP_PLANES, DUMP_MAX_NZ, DUMP_MAX_MAP = 8, 4, 4096, 1024
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_boxes(shape):
+    """[(z0, z1, y0, y1, x0, x1)] of the sample: the same for every cube of this shape."""
+    Nz, Ny, Nx = shape
+    rng = np.random.default_rng(DUMP_SEED)
+    nz, by, bx = min(Nz, DUMP_MAX_NZ), min(Ny, 4), min(Nx, 4)
+    py, px = min(Ny, 128), min(Nx, 128)
+    boxes = []
+    for _ in range(DUMP_BOXES):
+        z0 = int(rng.integers(0, Nz - nz + 1))
+        y0, x0 = int(rng.integers(0, Ny - by + 1)), int(rng.integers(0, Nx - bx + 1))
+        boxes.append((z0, z0 + nz, y0, y0 + by, x0, x0 + bx))
+    for _ in range(DUMP_PLANES):
+        z0 = int(rng.integers(0, Nz))
+        y0, x0 = int(rng.integers(0, Ny - py + 1)), int(rng.integers(0, Nx - px + 1))
+        boxes.append((z0, z0 + 1, y0, y0 + py, x0, x0 + px))
+    return boxes
+
+
+def box_to_host(a, z0, z1, y0, y1, x0, x1):
+    """Host copy of a[z0:z1, y0:y1, x0:x1] of a (Nz, Ny, Nx) device array: packed on the device
+    first (one copy kernel), then one device -> host copy."""
+    Nz, Ny, Nx = a.shape
+    if not (0 <= z0 < z1 <= Nz and 0 <= y0 < y1 <= Ny and 0 <= x0 < x1 <= Nx):
+        raise ValueError(f"box [{z0}:{z1}, {y0}:{y1}, {x0}:{x1}] outside {a.shape}")
+    if z1 - z0 == 1:
+        return a.window(y0, y1, x0, x1, z0, z1)
+    from origin_amd import _capi
+    nz, ny, nx = z1 - z0, y1 - y0, x1 - x0
+    es = a.dtype.itemsize
+    tmp = a.ctx.empty((nz, ny, nx), a.dtype)
+    try:
+        _capi.call("origin_copy_box", a.ctx.handle, 2, tmp.p, nx, ny * nx,
+                   C.c_void_p(a.ptr + ((z0 * Ny + y0) * Nx + x0) * es), Nx, Ny * Nx, nz, ny, nx, es)
+        return tmp.to_host()
+    finally:
+        tmp.free()
+
+
+def dump_outputs(dirname, cubes, maps, vectors):
+    """What the last timed step computed, as float32 / float64 .npy files (see the docstring)."""
+    shape = next(iter(cubes.values())).shape
+    boxes = dump_boxes(shape)
+    index = np.concatenate([np.ravel_multi_index(np.mgrid[z0:z1, y0:y1, x0:x1].reshape(3, -1),
+                                                 shape) for z0, z1, y0, y1, x0, x1 in boxes])
+    out = {"sample_index": index.astype(np.float64)}
+    for name, a in cubes.items():
+        if hasattr(a, "entries"):    # local maxima as lists: the sample looked up in them
+            idx, val = a.entries()
+            pos = np.minimum(np.searchsorted(idx, index), max(len(idx) - 1, 0))
+            hit = (idx[pos] == index) if len(idx) else np.zeros(index.shape, bool)
+            out[name] = np.where(hit, val[pos] if len(idx) else 0.0, 0.0).astype(np.float32)
+        else:
+            out[name] = np.concatenate([box_to_host(a, *b).reshape(-1) for b in boxes]
+                                       ).astype(np.float32)
+    for name, m in maps.items():
+        m = np.asarray(m)[:DUMP_MAX_MAP, :DUMP_MAX_MAP]
+        out[name] = m.astype(np.float32 if m.dtype == np.float32 else np.float64)
+    for name, v in vectors.items():
+        out[name] = np.asarray(v, dtype=np.float64).reshape(-1)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh interpreters of this
     script (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one GPU each), relay rank 0's JSON
@@ -147,18 +284,27 @@ def main():
     ap.add_argument("--size", type=int, default=600, help="field is size x size spaxels")
     ap.add_argument("--nz", type=int, default=3681)
     ap.add_argument("--nprof", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle check, the CPU baseline, the "
+                         "PCIe-inclusive pass, the runs without the local maxima and in the "
+                         "sequential form, per-kernel tables, roofline and per-rank blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (one rank "
+                         "only; the cubes as a fixed, seeded sample of voxels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="(--full) leave the CPU baseline out")
     ap.add_argument("--cpu-crop", type=int, default=100,
                     help="side of the centred crop the CPU oracle is timed on (SURVEY 8d: one "
                          "100x100 area)")
-    ap.add_argument("--check", choices=("off", "light", "full", "glr"), default="light",
-                    help="oracle check of the arrays the timed steps produced (N=1 only): light = "
-                         "one haloed GLR window + one PCA area, full = three windows + two areas "
-                         "+ a DCT window, glr = the three GLR windows only "
-                         "(oracle/window_check.py)")
-    ap.add_argument("--e2e-size", type=int, default=300,
-                    help="side of the sub-field for the PCIe-inclusive pass (host arrays in, host "
-                         "arrays out through the Step seam); 0 = skip")
+    ap.add_argument("--check", choices=("off", "light", "full", "glr"), default=None,
+                    help="(--full; default light there) oracle check of the arrays the timed steps "
+                         "produced (N=1 only): light = one haloed GLR window + one PCA area, full "
+                         "= three windows + two areas + a DCT window, glr = the three GLR windows "
+                         "only (oracle/window_check.py)")
+    ap.add_argument("--e2e-size", type=int, default=None,
+                    help="(--full; default 300 there) side of the sub-field for the "
+                         "PCIe-inclusive pass (host arrays in, host arrays out through the Step "
+                         "seam); 0 = skip")
     ap.add_argument("--glr-precision", choices=("f16x2", "f32", "bf16"), default="f16x2")
     ap.add_argument("--no-tail-overlap", dest="tail_overlap", action="store_false",
                     help="greedy PCA, then the GLR (rounds 1-2); default: the GLR of the row bands "
@@ -185,6 +331,18 @@ def main():
                     help="side of the square PCA areas (development: 128 makes area rows "
                          "cache-line aligned)")
     args = ap.parse_args()
+    if not args.full and args.check not in (None, "off"):
+        ap.error("--check needs --full")
+    if not args.full and args.e2e_size:
+        ap.error("--e2e-size needs --full")
+    if args.dump_outputs is not None and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    if args.check is None:
+        args.check = "light" if args.full else "off"
+    if args.e2e_size is None:
+        args.e2e_size = 300 if args.full else 0
+    if not args.full:
+        args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
     # stdout must carry exactly ONE JSON line: anything libraries print there (RCCL banners) is
@@ -445,7 +603,7 @@ def main():
     for _ in range(args.warmup):
         one_step()
     ctx.prof_reset()
-    ctx.prof_enable(True)
+    ctx.prof_enable(args.full)   # (the kernel table of --full; a plain run times the steps only)
     phase.clear()
     barrier()
     ctx.sync()
@@ -462,10 +620,54 @@ def main():
     elapsed = t1 - t0
     if comm is not None:
         elapsed = comm.max_float(elapsed)
+    total_vox = float(Nz) * N * N
+    ms_per_step = 1e3 * elapsed / max(1, args.steps)
+    value = total_vox * args.steps / elapsed
+    glr_precision = (glr.plan if world > 1 else plan).precision
+    saved_phase = dict(phase)
+    if args.dump_outputs is not None:
+        lm_out = None
+        if sparse_lm:
+            lm_out = (last["out"]["local_max"], last["out"]["local_min"])
+        elif dense_lm:
+            lm_out = (lmax_buf, lmin_buf)
+        dump_outputs(args.dump_outputs, dict(
+            cube_std=cube_std, cont_dct=cont_dct, cube_faint=cube_faint, cube_correl=correl,
+            cube_correl_min=correl_min, cube_profile=profile,
+            **(dict(cube_local_max=lm_out[0], cube_local_min=lm_out[1]) if lm_out else {})),
+            dict(maxmap=last["out"]["maxmap"].to_host(), minmap=last["out"]["minmap"].to_host(),
+                 mapO2=last["mapO2"], ima_std=ima_std.to_host()),
+            {k: last["thr"][k] for k in ("thresO2", "meaO2", "stdO2")})
+    if not args.full:
+        if rank == 0:
+            line = {
+                "metric": METRIC,
+                "step": step_text(args, sparse_lm),
+                "value": round(value, 1),
+                "unit": "voxels/s",
+                "n_gpus": 1 if share_gpu else world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 3),
+                "ms_per_step_spread": spread(step_ms),
+                "higher_is_better": True,
+                "scaling": "strong",
+                "vs_baseline": None,
+                "dtype": dtype_text(glr_precision),
+                "data": "synthetic",
+                "config": config_block(args, Nz, N, glr_precision, world, comm, info, t_gen),
+                "full": False,
+                "wall_ms_per_step_by_phase": {k: round(1e3 * v / max(1, args.steps), 2)
+                                              for k, v in phase.items()},
+            }
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        barrier()
+        close_all(comm, [glr.plan] if world > 1 else [plan], ctx)
+        return
     prof = ctx.prof_report()
     # the same number of steps WITHOUT the local maxima -- the scope of the rounds-1/2 bench line
     # (DCT + thresholds + PCA + GLR), timed the same way, so that lines of different rounds compare
-    saved_phase = dict(phase)
     scope_r02 = None
     if args.local_max:
         barrier()
@@ -526,10 +728,6 @@ def main():
     phase.update(saved_phase)
     barrier()
 
-    total_vox = float(Nz) * N * N
-    ms_per_step = 1e3 * elapsed / max(1, args.steps)
-    value = total_vox * args.steps / elapsed
-
     # ---- roofline of the dominant kernel class (HIP events on the kernels' stream) ----
     local_vox = float(Nz) * ny * nx
     ntaps = sum(len(p) for p in kernels.prepare_profiles(field.profiles, 1e-8))
@@ -549,7 +747,6 @@ def main():
         "glr_spatial": ("mfma", 2.0 * 25 * 25 * local_vox),
         "glr_spectral": ("mfma", 2.0 * ntaps * local_vox),
     }
-    glr_precision = (glr.plan if world > 1 else plan).precision
     ext_vox = local_vox
     if world > 1:  # the GLR runs on the halo-extended tile
         ext_vox = float(Nz) * glr.eshape[1] * glr.eshape[2]
@@ -854,40 +1051,22 @@ def main():
 
     if rank == 0:
         line = {
-            "metric": "voxels/s through DCT+PCA+GLR (ORIGIN hot path)",
-            "step": "Preprocessing (DCT, standardise) -> PCA thresholds -> greedy PCA -> TGLR "
-                    "(correl, correl_min, profile, maxmap, minmap" +
-                    (", cube_local_max, cube_local_min" + (" as lists of their non-zero voxels)"
-                                                           if sparse_lm else ")")
-                     if args.local_max else ")"),
+            "metric": METRIC,
+            "step": step_text(args, sparse_lm),
             "value": round(value, 1),
             "unit": "voxels/s",
             "n_gpus": 1 if share_gpu else world,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
-            "ms_per_step_spread": {"min": round(min(step_ms), 3),
-                                   "median": round(float(np.median(step_ms)), 3),
-                                   "max": round(max(step_ms), 3), "n": len(step_ms),
-                                   "note": "wall time of each timed step on this rank (every step "
-                                           "ends with a synchronisation)"},
+            "ms_per_step_spread": spread(step_ms),
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
-            "dtype": "f32" if glr_precision == "f32" else f"f32+{glr_precision}",
+            "dtype": dtype_text(glr_precision),
             "data": "synthetic",
-            "config": {"workload": f"synthetic {Nz}x{N}x{N} cube, Dico_FWHM_2_12 "
-                                   f"({args.nprof} profiles), PSF 25x25, 100x100 areas, "
-                                   "dct_order 10, pfa 0.01, Noise_population 50, itermax 100",
-                       "arithmetic": "DCT/PCA: f32 storage, f64 reductions and eigen-solve; GLR: "
-                                     + {"f16x2": "two-term f16 split on the matrix cores, fp32 "
-                                                 "accumulate (fp32-class: 22 significant bits)",
-                                        "bf16": "single bf16 MFMA per product, fp32 accumulate",
-                                        "f32": "fp32 FMA"}.get(glr_precision, glr_precision),
-                       "masked_border": args.masked_border,
-                       "glr_spectral_arithmetic": glr_precision, "tiles": world, "comm": (comm.backend + (" " + comm.note if comm.note else ""))
-                       if comm is not None else None, "pca": info,
-                       "gen_seconds": round(t_gen, 1)},
+            "config": config_block(args, Nz, N, glr_precision, world, comm, info, t_gen),
+            "full": True,
             "without_local_max": scope_r02,
             "sequential": sequential,
             "roofline": roofline,
@@ -909,16 +1088,7 @@ def main():
         }
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
-    if comm is not None:
-        comm.close()
-    # plans and the context go before the interpreter does (origin_amd.device closes contexts at
-    # exit anyway; a context left to the HIP runtime's static destructors aborts the process)
-    for obj in ([glr.plan] if world > 1 else [plan]):
-        try:
-            obj.close()
-        except Exception:
-            pass
-    ctx.close()
+    close_all(comm, [glr.plan] if world > 1 else [plan], ctx)
 
 
 if __name__ == "__main__":

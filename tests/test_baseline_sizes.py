@@ -7,8 +7,8 @@ config 1  3681 x 200 x 200, DCT + greedy PCA: the whole HIP run against the orac
 config 2  3681 x 300 x 300, 20 profiles: the HIP chain on the full field, the oracle GLR on
           haloed (48+24)^2 windows of the device's own cube_faint at a corner, an edge and in the
           interior (lib_origin.py:1070-1217, steps.py:781-793).
-config 3  the 3681 x 600 x 600 headline workload: ``bench.py --check full`` (same windows + two
-          PCA areas + a DCT window), so that the number the driver records carries the same
+config 3  the 3681 x 600 x 600 headline workload: ``bench.py --full --check full`` (same windows
+          + two PCA areas + a DCT window), so that the number the driver records carries the same
           correctness bit.
 
 Tolerances: cube_std |d| <= 1e-5 max(1,|x|); cube_faint rel-Frobenius <= 2e-6 and
@@ -175,7 +175,7 @@ def test_masked_border_two_ranks_on_one_gpu():
     --masked-border 5`, host-staged strips): runs end to end, and the single-rank run of the same
     field passes its oracle check (DCT border window, corner area, GLR windows)."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "200", "--masked-border", "5",
-            "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--e2e-size", "0"]
+            "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--e2e-size", "0"]
     env = dict(os.environ, ORIGIN_BENCH_SHARE_GPU="1")
     r = subprocess.run(base + ["--gpus", "2", "--check", "off"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900, cwd=ROOT, env=env)
@@ -197,7 +197,7 @@ def test_config3_headline_600_bench_check():
     """bench.py on the headline workload with --check full: three GLR windows, two PCA areas
     and a DCT window of the very arrays the timed steps produced."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-           "--check", "full", "--no-cpu-baseline"]
+           "--full", "--check", "full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500,
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -214,8 +214,8 @@ def test_config5_900_bf16_bench_check():
     SURVEY 8c (|dT| <= 5e-2, rms <= 5e-3, arg-max mismatch <= 2 %); the PCA / DCT checks keep the
     fp32 tolerances."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "900", "--glr-precision",
-           "bf16", "--steps", "1", "--warmup", "1", "--check", "full", "--no-cpu-baseline",
-           "--e2e-size", "0"]
+           "bf16", "--steps", "1", "--warmup", "1", "--full", "--check", "full",
+           "--no-cpu-baseline", "--e2e-size", "0"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500,
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -235,7 +235,7 @@ def test_config5_900_f16x2_glr_windows_only():
     checked again (|dT| <= 1e-4) -- DCT and PCA do not depend on the GLR's arithmetic and were
     checked by the bf16 twin above."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "900", "--steps", "1",
-           "--warmup", "1", "--check", "glr", "--no-cpu-baseline", "--e2e-size", "0"]
+           "--warmup", "1", "--full", "--check", "glr", "--no-cpu-baseline", "--e2e-size", "0"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500,
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -255,7 +255,8 @@ def test_bench_two_ranks_on_one_gpu_prints_its_line():
     not first on the multi-GPU node."""
     env = dict(os.environ, ORIGIN_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "200",
-           "--steps", "2", "--warmup", "1", "--check", "off", "--no-cpu-baseline", "--e2e-size", "0"]
+           "--steps", "2", "--warmup", "1", "--full", "--check", "off", "--no-cpu-baseline",
+           "--e2e-size", "0"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT,
                        env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
