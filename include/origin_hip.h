@@ -339,7 +339,8 @@ int origin_glr_plan_destroy(origin_glr_plan *plan);
  * two-term f16 split of data and taps, three MFMAs per product, fp32 accumulation (~3e-7 of
  * sum |p x| from float64: fp32 class); 2 = bf16 operands, one MFMA per product (BASELINE config 4
  * "bf16 GLR"; |dT| ~1e-2); 0 = fp32 FMA chain (~1e-7).  Eligible: the spatial stage for odd PSF
- * sizes 5..25 (one field, or a mosaic of weighted fields: per-field accumulation); the spectral
+ * sizes 5..41 (27..41: three k-steps per window row, one block per CU for the f16 split; one
+ * field, or a mosaic of weighted fields: per-field accumulation); the spectral
  * stage for profile half widths <= 32 and K <= 26 -- through the border-class table without
  * weight maps, through the plan's norm cube with them (that cube, [Nz + 96][Ny][Nx] float32, is
  * allocated and filled by the plan's first run): the FOLD form where the cube is smooth along z
@@ -384,7 +385,7 @@ int origin_glr_mfma_count_model(int num_cu, int terms, int K, int n_narrow, int 
  * ORIGIN_GLR_SIDE_RESERVE, default an eighth of them; it starts behind everything the main stream was given before
  * the call).  origin_glr_run_finish makes the main stream wait for the side bands and writes the
  * maps (NULL: none).  Only plans whose two stages run the table kernels on the matrix cores
- * (one field, no weight maps, precision 1 or 2, PSF 5..25, profile half widths <= 32, K <= 26):
+ * (one field, no weight maps, precision 1 or 2, odd PSF 5..41, profile half widths <= 32, K <= 26):
  * origin_glr_rows_supported; others return ORIGIN_E_STATE. */
 #define ORIGIN_GLR_FIRST 1
 #define ORIGIN_GLR_SIDE 2

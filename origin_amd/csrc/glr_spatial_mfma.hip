@@ -30,10 +30,16 @@
 //
 // TERMS = 1: bf16 operands, one MFMA per k-step (BASELINE config 4's bf16 GLR), no scaling.
 //
-// Eligible shapes: odd P from 5 to 25 (float4 tile loads when P/2 is a multiple of four; any
-// field size: 16-byte accesses when Nx % 4 == 0, element
-// accesses otherwise), one field or a mosaic of weighted fields (WEIGHTED); other PSF sizes stay
-// on spatial4x4_kernel / spatial_kernel.
+// Large PSFs (P = 27 .. 41, the same kernel with SOLO blocks only): the window is 8 + P - 1 = 34
+// .. 48 columns, THREE k-steps per window row, (P + 3) x 3 k-steps per channel; a table entry
+// holds 56 taps (112 bytes, 7 x 16: odd, so the 16 entries a ds_read_b128 serves at once still
+// fall on distinct bank quads).  The f16 split group takes 99.5 KB (P = 27) .. 147.5 KB (P = 41)
+// of LDS: ONE block (4 waves, one per SIMD) per CU; the bf16 group (51 .. 77 KB) keeps two.
+//
+// Eligible shapes: odd P from 5 to 25 and the large sizes origin_spatial_mfma_ok admits (float4
+// tile loads when P/2 is a multiple of four; any field size: 16-byte accesses when Nx % 4 == 0,
+// element accesses otherwise), one field or a mosaic of weighted fields (WEIGHTED); other PSF
+// sizes stay on spatial4x4_kernel / spatial_kernel.
 #include <algorithm>
 #include <cstdlib>
 
@@ -52,7 +58,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int S2_R = 64;           // region side (outputs) of a block
 constexpr int S2_TAP_LOG2 = 12;    // f16 taps are stored times 2^12
-constexpr int S2_ENTRY = 80;       // bytes of one (row, copy) table entry: 40 taps, 5 groups of 8
+constexpr int S2_PMAX = 41;        // largest PSF the geometry below serves
+constexpr int S2_LDS_CU = 160 * 1024;  // LDS of a CU
 
 // -DS2_TIMING: clock64 stamps of block (1, 1, 0), phases 10..25, every wave
 // (tools/s2_phase_times.py; each stamp costs an s_memtime round trip and drains the LDS queue:
@@ -74,25 +81,40 @@ struct S2Geom {
   static constexpr int IW = (S2_R + H + 3) / 4 * 4, IH = S2_R + H;
   static constexpr int WROWS = 4 + H;                   // window rows of a patch
   static constexpr int WCOLS = 8 + H;                   // window columns (<= 32)
-  static constexpr int KROW = (WCOLS + 15) / 16;        // k-steps per window row
+  static constexpr int KROW = (WCOLS + 15) / 16;        // k-steps per window row (<= 3)
+  // bytes of one (row, copy) table entry, whose k-step reads cover its first 32 KROW bytes:
+  // 80 (40 taps) for KROW <= 2, 112 (56 taps) for KROW = 3
+  static constexpr int NG8 = KROW <= 2 ? 5 : 2 * KROW + 1;
+  static constexpr int ENTRY = 16 * NG8;
   static constexpr int NKS = WROWS * KROW;              // k-steps per channel
   static constexpr int PITCH = ((IW * 2 + 63) / 64) * 64 + 16;  // bytes, = 16 mod 64, > 2 IW
   static constexpr int IMG = IH * PITCH;                // one f16 / bf16 image
   static constexpr int TROWS = P + 6;                   // table rows: dy = -3 .. P + 2
-  static constexpr int TAB = TROWS * 8 * S2_ENTRY;      // one table (hi or lo)
+  static constexpr int TAB = TROWS * 8 * ENTRY;         // one table (hi or lo)
   static constexpr int NQ = (IW / 4 * IH + 255) / 256;  // staged float4 per thread of a group
   static constexpr int NT = (P * P + 255) / 256;        // staged taps per thread
   // (staged taps, row pitch P: the table build's reads of four rows per 32-lane group meet on banks
   // for P = 25; a pitch of 40 floats -- banks 8 dy + copy, all distinct -- was measured in round 3:
   // 8.15-8.2 ms either way, the conversion group's conflicts are not on the critical path)
   static constexpr int TAPS = (P * P * 4 + 15) / 16 * 16;
-  static_assert(IW % 4 == 0 && WCOLS <= 32 && PITCH >= 2 * IW + 16, "geometry");
+  static_assert(IW % 4 == 0 && WCOLS <= 48 && PITCH >= 2 * IW + 16, "geometry");
+  // B reads reach column 56 + 16 KROW (exclusive) of an image row, A reads byte 32 KROW
+  // (exclusive) of an entry; entries of an odd number of 16-byte groups: conflict-free A reads
+  static_assert(PITCH >= 2 * (56 + 16 * KROW) && 32 * KROW <= ENTRY && (NG8 & 1), "geometry");
 };
 
 template <int P, int TERMS>
 constexpr size_t s2_group_bytes() {
   using G = S2Geom<P>;
   return (size_t)(TERMS == 3 ? 2 : 1) * (G::IMG + G::TAB) + G::TAPS + 16;
+}
+
+// SOLO blocks a CU holds at a time: two up to P = 25 and for the bf16 image of a large P without
+// weight map; one for the f16 split of a large P (LDS) and the weighted bf16 one (registers: at
+// 256 VGPRs its element-wise staging spills) -- the launch bounds let those take a whole SIMD
+template <int P, int TERMS, bool WEIGHTED>
+constexpr int s2_solo_per_cu() {
+  return P <= 25 || (TERMS == 1 && !WEIGHTED) ? 2 : 1;
 }
 
 // two-term split of y into f16 hi + lo
@@ -114,7 +136,7 @@ __device__ __forceinline__ void s2_split(float y, _Float16 &hi, _Float16 &lo) {
 // cycles and CU, the matrix pipe ~55 % busy.  Two independent blocks drift apart and fill each
 // other's gaps: everything around a block's k-step loop runs beside the other block's MFMAs.
 template <int P, int TERMS, bool VEC, bool WEIGHTED, bool SOLO = false>
-__global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 2 : 1) void spatial2_kernel(const float *__restrict__ A,
+__global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, WEIGHTED>() : 1)) void spatial2_kernel(const float *__restrict__ A,
                                                           const float *__restrict__ W,
                                                           const float *__restrict__ taps, int Nz,
                                                           int Ny, int Nx, int zper, int accf,
@@ -240,13 +262,13 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 2 : 1) void spatial2_kerne
       }
     }
     S2_STAMP(5);
-    // table entry (row t = dy + 3, copy cp): G_dy[e + cp], e = 0..39, G_dy[e] = k[dy][e - 7]
+    // table entry (row t = dy + 3, copy cp): G_dy[e + cp], e = 0..8 NG8 - 1, G_dy[e] = k[dy][e - 7]
     for (int ent = gt; ent < P * 8; ent += 256) {
       const int dy = ent >> 3, cp = ent & 7;
-      char *dst_h = tab_h + ((dy + 3) * 8 + cp) * S2_ENTRY;
-      char *dst_l = tab_l + ((dy + 3) * 8 + cp) * S2_ENTRY;
+      char *dst_h = tab_h + ((dy + 3) * 8 + cp) * G::ENTRY;
+      char *dst_l = tab_l + ((dy + 3) * 8 + cp) * G::ENTRY;
 #pragma unroll
-      for (int g8 = 0; g8 < 5; ++g8) {
+      for (int g8 = 0; g8 < G::NG8; ++g8) {
         float t[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -281,7 +303,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 2 : 1) void spatial2_kerne
   const int mx = n & 7, my = n >> 3;              // output of row m = n (A operand: lane = row)
   // A: entry (row wy - my + 3, copy 7 - mx), group 2 half + h;  B: image row 32 ay + oy + wy,
   // columns 32 ax + ox + 16 half + 8 h + j
-  const int a_off = ((3 - my) * 8 + (7 - mx)) * S2_ENTRY + 16 * h;
+  const int a_off = ((3 - my) * 8 + (7 - mx)) * G::ENTRY + 16 * h;
   const int b_off = (32 * ay + oy) * G::PITCH + (32 * ax + ox + 8 * h) * 2;
   auto mfma_phase = [&](int z, float inv) {
     f32x16 acc;
@@ -293,7 +315,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 2 : 1) void spatial2_kerne
     u32x4v fah[DEPTH + 1], fal[DEPTH + 1], fbh[DEPTH + 1], fbl[DEPTH + 1];
     auto fetch = [&](int ks, int slot) {
       const int wy = ks / G::KROW, half = ks - wy * G::KROW;
-      const int ao = wy * 8 * S2_ENTRY + half * 32, bo = wy * G::PITCH + half * 32;
+      const int ao = wy * 8 * G::ENTRY + half * 32, bo = wy * G::PITCH + half * 32;
       fah[slot] = *reinterpret_cast<const u32x4v *>(ap + ao);
       fbh[slot] = *reinterpret_cast<const u32x4v *>(bp + bo);
       if constexpr (TERMS == 3) {
@@ -411,16 +433,17 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 2 : 1) void spatial2_kerne
 
 // 1 if this shape can run on spatial2_kernel
 int origin_spatial_mfma_ok(int Ny, int Nx, int P) {
-  return P >= 5 && P <= 25 && (P & 1) && Nx >= 1 && Ny >= 1;
+  return P >= 5 && P <= S2_PMAX && (P & 1) && Nx >= 1 && Ny >= 1;
 }
 
 template <int P, int TERMS, bool VEC, bool WEIGHTED>
 static int s2_launch(origin_ctx *ctx, const float *A, const float *W, const float *taps, int Nz,
                      int Ny, int Nx, int accf, float *out, int ry0, int nry, int rx0, int nrx) {
-  // ORIGIN_GLR_SPATIAL_SOLO=0: the two-group block of rounds 2-3
+  // ORIGIN_GLR_SPATIAL_SOLO=0: the two-group block of rounds 2-3 (P <= 25; two groups of a
+  // larger P do not fit the LDS of a CU)
   static const bool solo = !(getenv("ORIGIN_GLR_SPATIAL_SOLO") && atoi(getenv("ORIGIN_GLR_SPATIAL_SOLO")) == 0);
-  if (solo) {
-    const size_t lds1 = s2_group_bytes<P, TERMS>();
+  if (P > 25 || solo) {
+    constexpr size_t lds1 = s2_group_bytes<P, TERMS>();
     static OriginPerDeviceOnce attr1;
     ORIGIN_ONCE_PER_DEVICE(ctx, attr1,
                            ORIGIN_HIP(hipFuncSetAttribute(
@@ -429,7 +452,9 @@ static int s2_launch(origin_ctx *ctx, const float *A, const float *W, const floa
     if (nry <= 0) ry0 = 0, nry = cdiv(Ny, S2_R);
     if (nrx <= 0) rx0 = 0, nrx = cdiv(Nx, S2_R);
     const long regions = (long)nrx * nry;
-    const int slots = 2 * std::max(1, ctx->num_cu);  // two blocks per CU at a time
+    constexpr int per_cu = s2_solo_per_cu<P, TERMS, WEIGHTED>();  // blocks per CU at a time
+    static_assert(per_cu * lds1 <= (size_t)S2_LDS_CU, "LDS");
+    const int slots = per_cu * std::max(1, ctx->num_cu);
     int best_nzb = 1;
     double best_eff = 0.0;
     for (int nzb = 1; nzb <= std::max(1, Nz / 16); ++nzb) {
@@ -447,35 +472,37 @@ static int s2_launch(origin_ctx *ctx, const float *A, const float *W, const floa
     ORIGIN_LAUNCH_CHECK();
     return ORIGIN_OK;
   }
-  const size_t lds = 2 * s2_group_bytes<P, TERMS>();
-  static OriginPerDeviceOnce attr_once;
-  ORIGIN_ONCE_PER_DEVICE(ctx, attr_once,
-                         ORIGIN_HIP(hipFuncSetAttribute(
-                             (const void *)spatial2_kernel<P, TERMS, VEC, WEIGHTED>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
-  // one block per CU at a time (LDS): choose the number of z chunks so that the blocks fill
-  // whole rounds of the chip (an even number of channels per chunk keeps both groups busy)
-  if (nry <= 0) ry0 = 0, nry = cdiv(Ny, S2_R);
-  if (nrx <= 0) rx0 = 0, nrx = cdiv(Nx, S2_R);
-  const long regions = (long)nrx * nry;
-  const int ncu = std::max(1, ctx->num_cu);
-  int best_nzb = 1;
-  double best_eff = 0.0;
-  for (int nzb = 1; nzb <= std::max(1, Nz / 32); ++nzb) {
-    int zp = cdiv(Nz, nzb);
-    zp += zp & 1;
-    const long blocks = regions * cdiv(Nz, zp);
-    const long rounds = (blocks + ncu - 1) / ncu;
-    // useful channel slots / (rounds x chunk length x CUs), with a per-block cost of ~3 channels
-    const double eff = (double)regions * Nz / ((double)rounds * ncu * (zp + 3));
-    if (eff > best_eff) best_eff = eff, best_nzb = nzb;
+  if constexpr (P <= 25) {
+    const size_t lds = 2 * s2_group_bytes<P, TERMS>();
+    static OriginPerDeviceOnce attr_once;
+    ORIGIN_ONCE_PER_DEVICE(ctx, attr_once,
+                           ORIGIN_HIP(hipFuncSetAttribute(
+                               (const void *)spatial2_kernel<P, TERMS, VEC, WEIGHTED>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
+    // one block per CU at a time (LDS): choose the number of z chunks so that the blocks fill
+    // whole rounds of the chip (an even number of channels per chunk keeps both groups busy)
+    if (nry <= 0) ry0 = 0, nry = cdiv(Ny, S2_R);
+    if (nrx <= 0) rx0 = 0, nrx = cdiv(Nx, S2_R);
+    const long regions = (long)nrx * nry;
+    const int ncu = std::max(1, ctx->num_cu);
+    int best_nzb = 1;
+    double best_eff = 0.0;
+    for (int nzb = 1; nzb <= std::max(1, Nz / 32); ++nzb) {
+      int zp = cdiv(Nz, nzb);
+      zp += zp & 1;
+      const long blocks = regions * cdiv(Nz, zp);
+      const long rounds = (blocks + ncu - 1) / ncu;
+      // useful channel slots / (rounds x chunk length x CUs), with a per-block cost of ~3 channels
+      const double eff = (double)regions * Nz / ((double)rounds * ncu * (zp + 3));
+      if (eff > best_eff) best_eff = eff, best_nzb = nzb;
+    }
+    int zper = cdiv(Nz, best_nzb);
+    zper += zper & 1;
+    dim3 grid(nrx, nry, cdiv(Nz, zper));
+    hipLaunchKernelGGL((spatial2_kernel<P, TERMS, VEC, WEIGHTED>), grid, dim3(512), lds, ctx->stream,
+                       A, W, taps, Nz, Ny, Nx, zper, accf, out, ry0, rx0);
+    ORIGIN_LAUNCH_CHECK();
   }
-  int zper = cdiv(Nz, best_nzb);
-  zper += zper & 1;
-  dim3 grid(nrx, nry, cdiv(Nz, zper));
-  hipLaunchKernelGGL((spatial2_kernel<P, TERMS, VEC, WEIGHTED>), grid, dim3(512), lds, ctx->stream,
-                     A, W, taps, Nz, Ny, Nx, zper, accf, out, ry0, rx0);
-  ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }
 
@@ -518,6 +545,14 @@ int origin_spatial_mfma_launch(origin_ctx *ctx, int terms, const float *A, const
     S2_CASE_E(21);
     S2_CASE_E(23);
     S2_CASE(25);
+    S2_CASE_E(27);
+    S2_CASE_E(29);
+    S2_CASE_E(31);
+    S2_CASE(33);
+    S2_CASE_E(35);
+    S2_CASE_E(37);
+    S2_CASE_E(39);
+    S2_CASE(41);
   }
 #undef S2_CASE_E
 #undef S2_CASE
@@ -528,7 +563,8 @@ int origin_spatial_mfma_launch(origin_ctx *ctx, int terms, const float *A, const
 
 // MFMA instructions one launch issues (what SQ_INSTS_MFMA counts): every 64 x 64 region of the
 // field (partial ones at the edges included) runs, per channel, four waves of
-// (4 + P - 1) x ceil((8 + P - 1) / 16) k-steps with `terms` MFMAs each.
+// (4 + P - 1) x ceil((8 + P - 1) / 16) k-steps with `terms` MFMAs each (three k-steps per window
+// row for P >= 27).
 long origin_spatial_mfma_count(int terms, int Nz, int Ny, int Nx, int P) {
   const long regions = (long)cdiv(Nx, S2_R) * cdiv(Ny, S2_R);
   const long nks = (long)(4 + P - 1) * ((8 + P - 1 + 15) / 16);

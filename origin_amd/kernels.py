@@ -115,6 +115,12 @@ def prepare_profiles(profiles, pcut=None, pmeansub=True):
     return out
 
 
+# PSF sizes whose spatial stage runs on the matrix cores (mirrors origin_spatial_mfma_ok,
+# csrc/glr_spatial_mfma.hip): every odd size from 5 to 25 and the large ones measured faster
+# there than on the fp32 kernels
+SPATIAL_MFMA_SIZES = frozenset(range(5, 26, 2)) | frozenset(range(27, 42, 2))
+
+
 class GLRPlan:
     """Device-side constants of a GLR run: zero-mean PSFs, weights, prepared profiles and
     normalisation tables (include/origin_hip.h: origin_glr_plan)."""
@@ -173,7 +179,7 @@ class GLRPlan:
         # mirrors origin_spatial_mfma_ok (csrc/glr_spatial_mfma.hip): which spatial kernel runs
         # (weighted mosaics included: per-field accumulation on the matrix cores; their spectral
         # stage convolves the norm cube next to the data and stays in fp32)
-        self.spatial_on_matrix_cores = self.precision != "f32" and 5 <= self.P <= 25
+        self.spatial_on_matrix_cores = self.precision != "f32" and self.P in SPATIAL_MFMA_SIZES
         # (a weighted plan's spectral stage -- second Toeplitz product for the denominator,
         # csrc/glr_spectral_norm_mfma.hip -- exists for the f16 split only)
         self.spectral_on_matrix_cores = self.precision != "f32" and (
@@ -183,7 +189,8 @@ class GLRPlan:
     # -- the same run in row bands (include/origin_hip.h origin_glr_run_rows) ---------------
     def rows_supported(self):
         """Whether the plan's two stages run the table kernels on the matrix cores (one field,
-        no weight maps, PSF 5..25, half widths <= 32): only those plans run in row bands."""
+        no weight maps, a PSF size of SPATIAL_MFMA_SIZES, half widths <= 32): only those plans
+        run in row bands."""
         ok = C.c_int()
         _capi.call("origin_glr_rows_supported", self._h, C.byref(ok))
         return bool(ok.value)
