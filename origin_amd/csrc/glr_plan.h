@@ -1,0 +1,164 @@
+// The GLR plan, the table of what a plan runs, and the launch functions of the GLR stages: shared
+// by glr_plan.hip (plan), glr.hip (runs), glr_fp32.hip and the matrix-core kernels.
+#pragma once
+#include <cmath>
+#include <cstdlib>
+#include <vector>
+
+#include "common.h"
+#include "glr_tables.h"
+
+struct origin_glr_plan {
+  origin_ctx *ctx = nullptr;
+  int Nz = 0, Ny = 0, Nx = 0, nfields = 0, P = 0, K = 0;
+  int mode = 0;   // 0 = border-class table (weights=None), 1 = explicit norm cube
+  int lwmax = 0;  // largest profile half width
+  float *d_k = nullptr;     // [F][Nz][P][P]  zero-mean PSF
+  float *d_k2 = nullptr;    // [F][Nz][P][P]  its square
+  float *d_w = nullptr;     // [F][Ny][Nx] or null
+  float *d_taps = nullptr;  // concatenated profiles (odd lengths; even ones padded with a 0 tap)
+  float *d_taps2 = nullptr; // squares
+  int *d_tap_off = nullptr; // [K+1]
+  float *d_rden = nullptr;  // mode 0: [P*P][K][NzP]  1/sqrt(den) per border class (0 for z >= Nz)
+  int Kp = 0;               // z stride of d_rden (= NzP)
+  int symmetric = 0;   // every prepared profile is exactly symmetric about its centre
+  float *d_htaps = nullptr;  // symmetric case: half profiles h_k[d] = p_k[lw_k + d], d = 0..lw_k
+  int *d_htap_off = nullptr; // [K+1]
+  float *d_rows = nullptr;   // [K+1][RL] rows (lw, p[0..2 lw]) for spectral3_kernel<LWT>
+  float *d_rdi = nullptr;    // mode 0: interior-class slice of d_rden, [K][NzP] (not owned)
+  int *d_border = nullptr;   // mode 0: flat indices of the spaxels whose border class is not interior
+  int nborder = 0;
+  int lwt = 0;         // template half width chosen for d_rows (8, 16, 24, 29 or 32; 0 = none)
+  int NzP = 0;
+  uint4 *d_atab = nullptr;   // matrix-core spectral stage: shifted hi/lo f16 tap copies (glr_tables.h)
+  uint4 *d_atab_bf16 = nullptr;  // the same with bf16 taps (precision 2)
+  uint4 *d_atab2 = nullptr;      // the squared taps in the same layout (plans with an explicit norm cube)
+  int *d_pwide = nullptr;  // [K] processing order, narrow first: original index | (half width > 16) << 8
+  int n_narrow = 0;    // number of narrow profiles (the first n_narrow slots)
+  int order_ident = 0; // the processing order is the caller's order (slot = index)
+  float *d_rdi_s = nullptr;  // interior-class 1/sqrt(den) in processing order [slot][NzP]
+  // FOLD (glr_spectral_mfma.hip): taps times a_k = 1/sqrt(sum p_k^2), the table 1/(a_k sqrt(den))
+  // [P*P][K][NzP], the class factors s [P*P][NzP]; fold_eps = max |1/(a_k sqrt(den)) / s - 1| over
+  // the FOLD channels (the tables are dropped when it exceeds MF_FOLD_EPS; +inf: not measured)
+  uint4 *d_atab_fold = nullptr, *d_atab_bf16_fold = nullptr;
+  float *d_rden_fold = nullptr, *d_sden = nullptr;
+  float fold_eps = INFINITY;
+  // mode 1 (explicit norm cube): 1 once the first run has measured eps on the norm cube (then
+  // fold_eps holds it) -- NORMW runs where it is <= MF_FOLD_EPS
+  int normw_checked = 0;
+  std::vector<int> h_order;  // processing order on the host (empty: no matrix-core tap tables)
+  int precision = 0;  // 0 = fp32 FMA kernels, 1 = split-f16 MFMA stages, 2 = bf16 MFMA stages
+  float *d_normc = nullptr;  // mode 1: norm_fsf [Nz][Ny][Nx], a constant of the plan (PSFs and weight
+                             // maps only): allocated with the plan, computed by the first run and kept
+  int normc_ready = 0;
+  size_t bytes = 0;
+};
+
+// ---- what a plan runs: the ONE place that decides it (run, row bands, MFMA counts, precision)
+enum GlrSpectral {
+  GLR_SPEC_TABLE,      // matrix cores, 1/sqrt(den) from the border-class tables (FOLD where it holds)
+  GLR_SPEC_NORMW,      // norm cube: FOLD form of the table kernel, two-product kernel at the ends
+  GLR_SPEC_NORM_MFMA,  // norm cube: two Toeplitz products on the matrix cores
+  GLR_SPEC_PACKED,     // fp32, two spaxels per lane, interior class + border pass
+  GLR_SPEC_FP32,       // fp32, register window of half width 8 / 16 / 32
+  GLR_SPEC_GENERIC     // fp32, plain loops (profiles wider than 32)
+};
+struct GlrPaths {
+  bool spatial_mfma;  // the spatial stage runs on the matrix cores
+  GlrSpectral spectral;
+  bool spectral_mfma() const { return spectral <= GLR_SPEC_NORM_MFMA; }
+  // runs in row bands / rectangles: both stages on the table kernels of the matrix cores
+  bool rows_ok() const { return spatial_mfma && spectral == GLR_SPEC_TABLE; }
+};
+// ORIGIN_GLR_NO_FOLD=1: the exact form everywhere (read per call: tests set it within a process)
+inline bool glr_no_fold() { return getenv("ORIGIN_GLR_NO_FOLD") != nullptr; }
+GlrPaths glr_paths_at(const origin_glr_plan *pl, int precision, bool no_fold);  // at a precision
+inline GlrPaths glr_paths(const origin_glr_plan *pl, bool no_fold) {
+  return glr_paths_at(pl, pl->precision, no_fold);
+}
+
+// ---- the work buffer of a run: [pad | cube_fsf | pad | partial maps]; the pads are MF_PAD_FRONT
+// and MF_PAD_BACK zero channels, the partial maps <= 64 rows each of maxima and minima
+struct GlrWork {
+  float *fsf, *back_pad, *part;
+  GlrWork(const origin_glr_plan *pl, float *d_work) {
+    const size_t S = (size_t)pl->Ny * pl->Nx;
+    fsf = d_work + MF_PAD_FRONT * S;
+    back_pad = fsf + (size_t)pl->Nz * S;
+    part = back_pad + MF_PAD_BACK * S;
+  }
+  static size_t elems(const origin_glr_plan *pl) {
+    const size_t S = (size_t)pl->Ny * pl->Nx;
+    return (size_t)pl->Nz * S + 2 * 64 * S + (MF_PAD_FRONT + MF_PAD_BACK) * S;
+  }
+};
+
+// glr_plan.hip: eps of the FOLD form on the norm cube a weighted plan's first run has just made
+int glr_plan_measure_normw_eps(origin_ctx *ctx, origin_glr_plan *pl, const float *norm);
+
+// ---- glr_fp32.hip: the fp32 FMA kernels
+// out (+)= corr2(A * B, taps) per channel; A == NULL: the norm of the weights B
+int glr_fp32_spatial(origin_ctx *ctx, const float *A, const float *B, const float *taps, int Nz,
+                     int Ny, int Nx, int P, int accumulate, float *out);
+// what the spectral stage reads and writes, whatever kernel runs it; a launch reports the rows of
+// its partial maps (nzc rows each at pmax / pmin, null without want_maps)
+struct GlrSpectralIO {
+  const float *fsf, *norm;  // padded cubes, channel 0 (norm: plans with a norm cube)
+  const uint8_t *mask;
+  float *correl;
+  uint8_t *profile;
+  float *correl_min;
+  float *part;
+  bool want_maps;
+  int nzc = 0;  // set by the launch
+  float *pmax = nullptr, *pmin = nullptr;
+};
+// forms PACKED (with its border pass, timed as K_GLR_BORDER), FP32 and GENERIC
+int glr_fp32_spectral(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form,
+                      GlrSpectralIO *io, ProfScope *ps);
+// PACKED: the maps of the border spaxels from the final cubes (behind maxmap_final_kernel)
+int glr_fp32_border_maps(origin_ctx *ctx, const origin_glr_plan *pl, const float *correl,
+                         const float *correl_min, float *maxmap, float *minmap);
+
+// ---- glr_spectral_mfma.hip
+struct SpectralMfmaArgs {
+  // cube and outputs
+  GlrSpectralIO *io;
+  // tables (fold: nullptr = the exact form everywhere)
+  int terms;  // 3: f16 split, 1: bf16
+  const uint4 *atab, *atab_fold;
+  const float *rden, *rdi_s, *rden_fold, *sden;
+  const int *pinfo;
+  int NzP, K, n_narrow, ident;
+  // geometry
+  int Nz, Ny, Nx, P;
+  // range (s_count > 0: spaxels s_first .. s_first + s_count - 1) or rectangle (rx1 > 0: columns
+  // rx0 .. rx1 - 1 of the range's rows); neither: the whole field
+  long s_first = 0, s_count = 0;
+  int rx0 = 0, rx1 = 0;
+  // NORMW: the norm cube, and the rows of each partial map when other launches add theirs
+  const float *normc = nullptr;
+  int part_rows = 0;
+};
+// the tables of the plan's precision; fold: bring the folded tables too
+SpectralMfmaArgs glr_spectral_mfma_args(const origin_glr_plan *pl, GlrSpectralIO *io, bool fold);
+int origin_spectral_mfma_launch(origin_ctx *ctx, const SpectralMfmaArgs &a);
+long origin_spectral_mfma_count(int num_cu, int terms, int K, int n_narrow, int Nz, int Ny,
+                                int Nx);
+int origin_spectral_mfma_chunks(int num_cu, int Nz, int Ny, int Nx);
+
+// ---- glr_spectral_norm_mfma.hip: the same stage for plans with an explicit norm cube
+int origin_spectral_norm_mfma_max_k();
+int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const float *norm,
+                                     const uint4 *atab, const uint4 *atab2, const int *pinfo, int K,
+                                     int Nz, int Ny, int Nx, const uint8_t *mask, float *correl,
+                                     uint8_t *profile, float *correl_min, float *part,
+                                     bool want_maps, int *nzc_out, float **pmax_out,
+                                     float **pmin_out);
+// the end tiles [0, zf0) and [zf1, Nz) of a plan whose other channels run NORMW
+int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const float *fsf, const float *norm,
+                                          const uint4 *atab, const uint4 *atab2, const int *pinfo,
+                                          int K, int Nz, int Ny, int Nx, const uint8_t *mask,
+                                          float *correl, uint8_t *profile, float *correl_min,
+                                          float *pmax, float *pmin, int zf0, int zf1, int prow0,
+                                          int *rows_out);

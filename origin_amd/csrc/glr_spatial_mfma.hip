@@ -18,30 +18,28 @@
 //     the zero-padded row shifted by 0..7 elements (entry pitch 80 bytes: conflict free), rows
 //     -3..-1 and P..P+2 all zero for the outputs of a patch whose my puts wy - my outside.
 //
-// The PSF differs per channel, so image AND table change with every channel.  A block (8 waves
-// = two groups of 4) owns a 64 x 64 region and marches z; the groups take alternate channels and
-// alternate ROLES, separated by one block barrier per phase: while one group issues the 168
-// MFMAs of its channel (one wave per SIMD: the matrix pipe's full rate), the other converts its
-// next channel's input tile to the f16 hi / lo images and builds its table (VALU + LDS writes:
-// ~2200 cycles against ~5400), then they swap.  Global loads of the tile after next and its
-// taps are issued at the start of a group's MFMA phase and land in registers; the tile's
-// power-of-two scale (max |x|) is reduced at the end of that phase, so the conversion phase
-// starts with everything at hand.  LDS: 2 x (36.6 KB images + 39.7 KB table + 2.5 KB taps).
+// The PSF differs per channel, so image AND table change with every channel.  A block (4 waves,
+// one per SIMD) owns a 64 x 64 region and marches z: per channel it converts the input tile to the
+// f16 hi / lo images and builds its table (VALU + LDS writes: ~2200 cycles), then issues the 168
+// MFMAs (~5400).  Global loads of the next tile and its taps are issued in front of the MFMAs and
+// land in registers; the tile's power-of-two scale (max |x|) is reduced behind them, so the next
+// conversion starts with everything at hand.  A CU holds TWO blocks (P <= 25) that drift apart:
+// one converts while the other multiplies.  LDS per block: 36.6 KB images + 39.7 KB table + 2.5 KB
+// taps.
 //
 // TERMS = 1: bf16 operands, one MFMA per k-step (BASELINE config 4's bf16 GLR), no scaling.
 //
-// Large PSFs (P = 27 .. 41, the same kernel with SOLO blocks only): the window is 8 + P - 1 = 34
+// Large PSFs (P = 27 .. 41, the same kernel): the window is 8 + P - 1 = 34
 // .. 48 columns, THREE k-steps per window row, (P + 3) x 3 k-steps per channel; a table entry
 // holds 56 taps (112 bytes, 7 x 16: odd, so the 16 entries a ds_read_b128 serves at once still
 // fall on distinct bank quads).  The f16 split group takes 99.5 KB (P = 27) .. 147.5 KB (P = 41)
-// of LDS: ONE block (4 waves, one per SIMD) per CU; the bf16 group (51 .. 77 KB) keeps two.
+// of LDS: ONE block per CU; the bf16 group (51 .. 77 KB) keeps two.
 //
 // Eligible shapes: odd P from 5 to 25 and the large sizes origin_spatial_mfma_ok admits (float4
 // tile loads when P/2 is a multiple of four; any field size: 16-byte accesses when Nx % 4 == 0,
 // element accesses otherwise), one field or a mosaic of weighted fields (WEIGHTED); other PSF
 // sizes stay on spatial4x4_kernel / spatial_kernel.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 
@@ -61,14 +59,14 @@ constexpr int S2_TAP_LOG2 = 12;    // f16 taps are stored times 2^12
 constexpr int S2_PMAX = 41;        // largest PSF the geometry below serves
 constexpr int S2_LDS_CU = 160 * 1024;  // LDS of a CU
 
-// -DS2_TIMING: clock64 stamps of block (1, 1, 0), phases 10..25, every wave
+// -DS2_TIMING: clock64 stamps of block (1, 1, 0), channels 10..25 of its chunk, every wave
 // (tools/s2_phase_times.py; each stamp costs an s_memtime round trip and drains the LDS queue:
 // read the numbers as shares, not as cycle counts)
 #ifdef S2_TIMING
-__device__ long long s2_tim[16 * 8 * 8];
+__device__ long long s2_tim[16 * 4 * 8];
 #define S2_STAMP(k)                                                                             \
   if (blockIdx.x == 1 && blockIdx.y == 1 && blockIdx.z == 0 && lane == 0 && p >= 10 && p < 26) \
-  s2_tim[((p - 10) * 8 + wave) * 8 + (k)] = clock64()
+  s2_tim[((p - 10) * 4 + wave) * 8 + (k)] = clock64()
 #else
 #define S2_STAMP(k)
 #endif
@@ -109,11 +107,11 @@ constexpr size_t s2_group_bytes() {
   return (size_t)(TERMS == 3 ? 2 : 1) * (G::IMG + G::TAB) + G::TAPS + 16;
 }
 
-// SOLO blocks a CU holds at a time: two up to P = 25 and for the bf16 image of a large P without
+// blocks a CU holds at a time: two up to P = 25 and for the bf16 image of a large P without
 // weight map; one for the f16 split of a large P (LDS) and the weighted bf16 one (registers: at
 // 256 VGPRs its element-wise staging spills) -- the launch bounds let those take a whole SIMD
 template <int P, int TERMS, bool WEIGHTED>
-constexpr int s2_solo_per_cu() {
+constexpr int s2_blocks_per_cu() {
   return P <= 25 || (TERMS == 1 && !WEIGHTED) ? 2 : 1;
 }
 
@@ -128,15 +126,13 @@ __device__ __forceinline__ void s2_split(float y, _Float16 &hi, _Float16 &lo) {
 // WEIGHTED: one field of a mosaic (lib_origin.py:1029-1031, :1134-1147): the input is cube * W
 // (W [Ny][Nx], the field's weight map, multiplied in while the tile is staged) and, with accf,
 // the result is added to what the fields before left in `out`.
-// SOLO (round 4): a block is ONE group of four waves (256 threads, half the LDS) that converts and
-// multiplies its channels one after the other, and a CU holds TWO such blocks.  The two-group
-// block keeps its groups in lock step (one block barrier per phase): while one group runs its MFMA
-// phase (~9.6 k cycles: 1.2 k of loads in front, 6.3 k of k-steps, 1.5 k of scale reduction and
-// stores behind) the other converts (2.2 k) and then WAITS at the barrier -- one channel per 9.6 k
-// cycles and CU, the matrix pipe ~55 % busy.  Two independent blocks drift apart and fill each
-// other's gaps: everything around a block's k-step loop runs beside the other block's MFMAs.
-template <int P, int TERMS, bool VEC, bool WEIGHTED, bool SOLO = false>
-__global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, WEIGHTED>() : 1)) void spatial2_kernel(const float *__restrict__ A,
+// A block is ONE group of four waves that converts and multiplies its channels one after the other,
+// and a CU holds two such blocks where they fit.  (A block of two groups in lock step -- one
+// converting while the other multiplies, a block barrier per phase -- kept the matrix pipe ~55 %
+// busy: the converting group waits at the barrier.  Two independent blocks drift apart and fill
+// each other's gaps.)
+template <int P, int TERMS, bool VEC, bool WEIGHTED>
+__global__ __launch_bounds__(256, (s2_blocks_per_cu<P, TERMS, WEIGHTED>())) void spatial2_kernel(const float *__restrict__ A,
                                                           const float *__restrict__ W,
                                                           const float *__restrict__ taps, int Nz,
                                                           int Ny, int Nx, int zper, int accf,
@@ -150,8 +146,8 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, 
   constexpr size_t GB = s2_group_bytes<P, TERMS>();
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = SOLO ? 0 : wave >> 2, gw = wave & 3, gt = tid & 255;  // group, wave / thread in group
-  char *base = s2_lds + grp * GB;
+  const int gw = wave & 3, gt = tid & 255;  // wave / thread in the group
+  char *base = s2_lds;
   char *img_h = base, *img_l = base + (TERMS == 3 ? G::IMG : 0);
   char *tab_h = base + (TERMS == 3 ? 2 : 1) * G::IMG, *tab_l = tab_h + (TERMS == 3 ? G::TAB : 0);
   float *tapst = reinterpret_cast<float *>(tab_h + (TERMS == 3 ? 2 : 1) * G::TAB);
@@ -163,10 +159,10 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, 
   const int n = lane & 31, h = lane >> 5;
 
   // ---- zero everything once: table rows outside the PSF stay zero for good, image pads finite
-  for (int i = tid; i < (int)((SOLO ? 1 : 2) * GB / 16); i += (SOLO ? 256 : 512))
+  for (int i = tid; i < (int)(GB / 16); i += 256)
     reinterpret_cast<uint4 *>(s2_lds)[i] = make_uint4(0u, 0u, 0u, 0u);
 
-  // ---- register staging of this group's NEXT channel: input tile, taps
+  // ---- register staging of the NEXT channel: input tile, taps
   float4 stage[G::NQ];
   float tapreg[G::NT];
   auto prefetch = [&](int z) {
@@ -223,7 +219,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, 
   };
 
   // ---- conversion phase: staged tile -> f16 hi / lo (or bf16) image; taps -> fragment table
-  int p = 0;  // phase counter (kernel scope: the timing stamps inside the lambdas name it)
+  int p = 0;  // channel counter (kernel scope: the timing stamps inside the lambdas name it)
   auto convert = [&](int slot, float &inv_out) {
     float scale = 1.f, inv = 1.f;
     if constexpr (TERMS == 3) {
@@ -231,7 +227,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, 
       const bool tiny = ex < 40 || ex == 255;  // zero / denormal-small / non-finite: no scaling
       scale = __uint_as_float((unsigned)(tiny ? 127 : 268 - ex) << 23);  // max |y| in [2^14, 2^15)
       inv = __uint_as_float((unsigned)(tiny ? 127 - S2_TAP_LOG2 : ex - 14 - S2_TAP_LOG2) << 23);
-      if (gt == 0) maxw[slot ^ 1] = 0u;  // the word the NEXT publish of this group adds to
+      if (gt == 0) maxw[slot ^ 1] = 0u;  // the word the NEXT publish adds to
     }
     inv_out = inv;
     S2_STAMP(4);
@@ -375,55 +371,27 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, (SOLO ? s2_solo_per_cu<P, TERMS, 
     }
   };
 
-  // ---- schedule.  Group g takes channels z0 + g + 2 i; in phase p it converts channel i when
-  // p = 2 i + g and runs the MFMAs of channel i when p = 2 i + g + 1.  One barrier per phase.
+  // ---- schedule, every channel of the chunk: convert (tile and taps are in registers / staging),
+  // barrier (image and table complete), request the next channel's tile and taps, MFMAs + stores,
+  // publish the next tile's maximum and taps, barrier (everybody is done reading image and table)
   const int nch = z1 - z0;
-  if constexpr (SOLO) {
-    // one group, every channel of the chunk: convert (tile and taps are in registers / staging),
-    // barrier (image and table complete), request the next channel's tile and taps, MFMAs + stores,
-    // publish the next tile's maximum and taps, barrier (everybody is done reading image and table)
-    __syncthreads();  // zero fill done
-    if (nch > 0) {
-      prefetch(z0);
-      publish(0);
-    }
-    __syncthreads();
-    float inv_s = 1.f;
-    for (int i = 0; i < nch; ++i) {
-      p = i;
-      convert(i & 1, inv_s);
-      __syncthreads();
-      if (i + 1 < nch) prefetch(z0 + i + 1);
-      mfma_phase(z0 + i, inv_s);
-      if (i + 1 < nch) publish((i + 1) & 1);
-      __syncthreads();
-    }
-    return;
-  }
-  const int ng = (nch - grp + 1) / 2;  // channels of this group
-  __syncthreads();                     // zero fill done
-  if (ng > 0) {
-    prefetch(z0 + grp);
+  __syncthreads();  // zero fill done
+  if (nch > 0) {
+    prefetch(z0);
     publish(0);
   }
   __syncthreads();
-  float inv_cur = 1.f;
-  const int nphase = 2 * ((nch + 1) / 2) + 2;
-  for (p = 0; p < nphase; ++p) {
-    const int q = p - grp;
+  float inv_s = 1.f;
+  for (int i = 0; i < nch; ++i) {
+    p = i;
     S2_STAMP(0);
-    if (q >= 0) {
-      const int i = q >> 1;
-      if ((q & 1) == 0) {
-        if (i < ng) convert(i & 1, inv_cur);
-      } else if (i < ng) {
-        if (i + 1 < ng) prefetch(z0 + grp + 2 * (i + 1));
-        S2_STAMP(1);
-        mfma_phase(z0 + grp + 2 * i, inv_cur);
-        S2_STAMP(2);
-        if (i + 1 < ng) publish((i + 1) & 1);
-      }
-    }
+    convert(i & 1, inv_s);
+    __syncthreads();
+    if (i + 1 < nch) prefetch(z0 + i + 1);
+    S2_STAMP(1);
+    mfma_phase(z0 + i, inv_s);
+    S2_STAMP(2);
+    if (i + 1 < nch) publish((i + 1) & 1);
     S2_STAMP(3);
     __syncthreads();
   }
@@ -439,70 +407,34 @@ int origin_spatial_mfma_ok(int Ny, int Nx, int P) {
 template <int P, int TERMS, bool VEC, bool WEIGHTED>
 static int s2_launch(origin_ctx *ctx, const float *A, const float *W, const float *taps, int Nz,
                      int Ny, int Nx, int accf, float *out, int ry0, int nry, int rx0, int nrx) {
-  // ORIGIN_GLR_SPATIAL_SOLO=0: the two-group block of rounds 2-3 (P <= 25; two groups of a
-  // larger P do not fit the LDS of a CU)
-  static const bool solo = !(getenv("ORIGIN_GLR_SPATIAL_SOLO") && atoi(getenv("ORIGIN_GLR_SPATIAL_SOLO")) == 0);
-  if (P > 25 || solo) {
-    constexpr size_t lds1 = s2_group_bytes<P, TERMS>();
-    static OriginPerDeviceOnce attr1;
-    ORIGIN_ONCE_PER_DEVICE(ctx, attr1,
-                           ORIGIN_HIP(hipFuncSetAttribute(
-                               (const void *)spatial2_kernel<P, TERMS, VEC, WEIGHTED, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)));
-    if (nry <= 0) ry0 = 0, nry = cdiv(Ny, S2_R);
-    if (nrx <= 0) rx0 = 0, nrx = cdiv(Nx, S2_R);
-    const long regions = (long)nrx * nry;
-    constexpr int per_cu = s2_solo_per_cu<P, TERMS, WEIGHTED>();  // blocks per CU at a time
-    static_assert(per_cu * lds1 <= (size_t)S2_LDS_CU, "LDS");
-    const int slots = per_cu * std::max(1, ctx->num_cu);
-    int best_nzb = 1;
-    double best_eff = 0.0;
-    for (int nzb = 1; nzb <= std::max(1, Nz / 16); ++nzb) {
-      const int zp = cdiv(Nz, nzb);
-      const long blocks = regions * cdiv(Nz, zp);
-      const long rounds = (blocks + slots - 1) / slots;
-      // useful channel slots / (rounds x chunk length x block slots), ~2 channels of start-up per block
-      const double eff = (double)regions * Nz / ((double)rounds * slots * (zp + 2));
-      if (eff > best_eff) best_eff = eff, best_nzb = nzb;
-    }
-    const int zper = cdiv(Nz, best_nzb);
-    dim3 grid(nrx, nry, cdiv(Nz, zper));
-    hipLaunchKernelGGL((spatial2_kernel<P, TERMS, VEC, WEIGHTED, true>), grid, dim3(256), lds1,
-                       ctx->stream, A, W, taps, Nz, Ny, Nx, zper, accf, out, ry0, rx0);
-    ORIGIN_LAUNCH_CHECK();
-    return ORIGIN_OK;
+  constexpr size_t lds = s2_group_bytes<P, TERMS>();
+  static OriginPerDeviceOnce attr_once;
+  ORIGIN_ONCE_PER_DEVICE(ctx, attr_once,
+                         ORIGIN_HIP(hipFuncSetAttribute(
+                             (const void *)spatial2_kernel<P, TERMS, VEC, WEIGHTED>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
+  if (nry <= 0) ry0 = 0, nry = cdiv(Ny, S2_R);
+  if (nrx <= 0) rx0 = 0, nrx = cdiv(Nx, S2_R);
+  // choose the number of z chunks so that the blocks fill whole rounds of the chip
+  const long regions = (long)nrx * nry;
+  constexpr int per_cu = s2_blocks_per_cu<P, TERMS, WEIGHTED>();  // blocks per CU at a time
+  static_assert(per_cu * lds <= (size_t)S2_LDS_CU, "LDS");
+  const int slots = per_cu * std::max(1, ctx->num_cu);
+  int best_nzb = 1;
+  double best_eff = 0.0;
+  for (int nzb = 1; nzb <= std::max(1, Nz / 16); ++nzb) {
+    const int zp = cdiv(Nz, nzb);
+    const long blocks = regions * cdiv(Nz, zp);
+    const long rounds = (blocks + slots - 1) / slots;
+    // useful channel slots / (rounds x chunk length x block slots), ~2 channels of start-up per block
+    const double eff = (double)regions * Nz / ((double)rounds * slots * (zp + 2));
+    if (eff > best_eff) best_eff = eff, best_nzb = nzb;
   }
-  if constexpr (P <= 25) {
-    const size_t lds = 2 * s2_group_bytes<P, TERMS>();
-    static OriginPerDeviceOnce attr_once;
-    ORIGIN_ONCE_PER_DEVICE(ctx, attr_once,
-                           ORIGIN_HIP(hipFuncSetAttribute(
-                               (const void *)spatial2_kernel<P, TERMS, VEC, WEIGHTED>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
-    // one block per CU at a time (LDS): choose the number of z chunks so that the blocks fill
-    // whole rounds of the chip (an even number of channels per chunk keeps both groups busy)
-    if (nry <= 0) ry0 = 0, nry = cdiv(Ny, S2_R);
-    if (nrx <= 0) rx0 = 0, nrx = cdiv(Nx, S2_R);
-    const long regions = (long)nrx * nry;
-    const int ncu = std::max(1, ctx->num_cu);
-    int best_nzb = 1;
-    double best_eff = 0.0;
-    for (int nzb = 1; nzb <= std::max(1, Nz / 32); ++nzb) {
-      int zp = cdiv(Nz, nzb);
-      zp += zp & 1;
-      const long blocks = regions * cdiv(Nz, zp);
-      const long rounds = (blocks + ncu - 1) / ncu;
-      // useful channel slots / (rounds x chunk length x CUs), with a per-block cost of ~3 channels
-      const double eff = (double)regions * Nz / ((double)rounds * ncu * (zp + 3));
-      if (eff > best_eff) best_eff = eff, best_nzb = nzb;
-    }
-    int zper = cdiv(Nz, best_nzb);
-    zper += zper & 1;
-    dim3 grid(nrx, nry, cdiv(Nz, zper));
-    hipLaunchKernelGGL((spatial2_kernel<P, TERMS, VEC, WEIGHTED>), grid, dim3(512), lds, ctx->stream,
-                       A, W, taps, Nz, Ny, Nx, zper, accf, out, ry0, rx0);
-    ORIGIN_LAUNCH_CHECK();
-  }
+  const int zper = cdiv(Nz, best_nzb);
+  dim3 grid(nrx, nry, cdiv(Nz, zper));
+  hipLaunchKernelGGL((spatial2_kernel<P, TERMS, VEC, WEIGHTED>), grid, dim3(256), lds, ctx->stream,
+                     A, W, taps, Nz, Ny, Nx, zper, accf, out, ry0, rx0);
+  ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }
 
@@ -573,6 +505,6 @@ long origin_spatial_mfma_count(int terms, int Nz, int Ny, int Nx, int P) {
 
 #ifdef S2_TIMING
 extern "C" int origin_debug_s2_timing(long long *out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(s2_tim), sizeof(long long) * 16 * 8 * 8);
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(s2_tim), sizeof(long long) * 16 * 4 * 8);
 }
 #endif

@@ -3,7 +3,7 @@
 // profile = first argmax_k, correl_min = min_k; ComputeTGLR.run's mask glue steps.py:781,788).
 //
 //   num_k[z] = sum_j p_k[j] x[z + lw_k - j]   is a banded Toeplitz product per profile whose
-//   data operand is shared by all K profiles (csrc/glr.hip has the derivation and the layout of
+//   data operand is shared by all K profiles (csrc/glr_plan.hip has the derivation and the layout of
 //   the tap table).  Here a tile is 16 output channels z0..z0+15 and the 32 rows of the MFMA hold
 //   a PAIR of profiles: rows 0-15 profile a, rows 16-31 profile b, against the window
 //   x[z0-32 .. z0+47] (five 16-channel blocks; pairs of narrow profiles -- half width <= 16 --
@@ -42,7 +42,7 @@
 //    s a factor of the lane's border class alone and |eps| a few 1e-7 wherever the PSF varies
 //    smoothly with the channel and the profile's support lies inside the cube (den_k is norm_fsf
 //    smoothed by p_k^2: what depends on k is the curvature of norm_fsf times the profile's
-//    variance).  The plan measures eps on its own tables (fold_tables_kernel, glr.hip: s = the
+//    variance).  The plan measures eps on its own tables (fold_tables_kernel, glr_plan.hip: s = the
 //    middle of the range over k, eps = half its relative width; 5.4e-7 for the benchmark's Moffat
 //    PSF and dictionary); where it is <= MF_FOLD_EPS = 2e-6 the taps carry a_k and the pair loop
 //    compares the bare accumulators -- 5 instead of 7 VALU instructions per output and pair, no
@@ -66,8 +66,7 @@
 //    2^+-4, exact in f16; a larger step re-converts the window): 12.4 -> 11.5 ms.
 #include <algorithm>
 
-#include "common.h"
-#include "glr_tables.h"
+#include "glr_plan.h"
 
 namespace {
 
@@ -78,7 +77,7 @@ constexpr bool SM_PREFETCH = MF_WAVES <= 8;
 // -DSM_TIMING: clock64 stamps of block (3, 1), every wave, tiles 2..9 of the chunk's FOLD range
 // (tools/sm_phase_times.py; a stamp is an s_memtime round trip: read the numbers as shares)
 #ifdef SM_TIMING
-__device__ long long sm_wave[4 * MF_WAVES * 4];  // blocks (3..6, 1): per wave start, end, columns taken
+__device__ long long sm_wave[4 * MF_WAVES * 3];  // blocks (3..6, 1): per wave start, end, wall ticks
 __device__ long long sm_tim[8 * MF_WAVES * 8];
 #define SM_STAMP(k)                                                                       \
   if (blockIdx.x == 3 && blockIdx.y == 1 && lane == 0 && sm_tile >= 2 && sm_tile < 10)    \
@@ -735,28 +734,22 @@ __global__ __launch_bounds__(64 * MF_WAVES, 1) void spectral_mfma2_kernel(
     const int *__restrict__ pinfo, int K, int NP, int Nz, int Ny, int Nx, int P, int zchunk, const uint8_t *__restrict__ mask, float *__restrict__ correl,
     uint8_t *__restrict__ profile, float *__restrict__ correl_min, float *__restrict__ part_max,
     float *__restrict__ part_min, const float *__restrict__ sden, int zf0, int zf1, int nN,
-    long s_first, long s_end_launch, int rx0, int rx1, int cols_per_block) {
-  // (s_first, s_end: the spaxels of this launch, in multiples of 32 from the field's first -- a run
+    long s_first, long s_end_launch, int rx0, int rx1) {
+  // (s_first, s_end_launch: the spaxels of this launch, in multiples of 32 from the field's first -- a run
   // may be split into row bands; waves hold the same 32 spaxels as in a launch over the field.
   // rx1 > 0: a RECTANGLE instead -- the rows s_first / Nx .. s_end / Nx, columns rx0 .. rx1 - 1 of
   // each; a wave holds 32 consecutive columns of one row)
-  // A block owns cols_per_block COLUMNS (32 spaxels x the chunk's channels) and its waves PULL them
-  // from a counter in LDS (round 4).  With one column per wave -- the form of rounds 2-3 -- the
-  // in-kernel clock stamps (-DSM_TIMING, profiles/r04_sm_phase_times.txt) showed the three waves
-  // of a SIMD taking 23 k / 32 k / 49 k cycles per tile: the issue arbiter serves the oldest wave
-  // first, the first wave of a SIMD is done with its nine tiles when the third has done four, and
-  // its slot stays empty until the block ends (the block holds the CU's LDS) -- 2.1 waves per SIMD
-  // on average, one alone at the end.  Pulled columns go to whoever is free.  (It evens out the
-  // waves and leaves the kernel's time where it was: see the launch.)
+  // A wave takes one COLUMN (32 spaxels x the chunk's channels): column blockIdx.x * MF_WAVES + wave.
+  // (Columns pulled from a counter in LDS by whichever wave is free were measured with 1 / 2 / 3 / 4
+  // / 6 columns per wave: 9.59 / 9.80 / 9.72 / 9.80 / 11.1 ms -- evening out the waves does not move
+  // the kernel: while a SIMD's first wave is gone the other two run that much faster.)
   extern __shared__ __align__(16) char sm_lds[];
-  __shared__ int sm_next_col;
   const int Kp = K + (K & 1);  // slots in LDS: an odd K's last profile twice (its pair partner)
   {
     constexpr int PV = MF_PROF_BYTES / 16;
     const int nvec = Kp * PV;
     for (int i = threadIdx.x; i < nvec; i += 64 * MF_WAVES)
       reinterpret_cast<uint4 *>(sm_lds)[i] = atab[i < K * PV ? i : i - PV];
-    if (threadIdx.x == 0) sm_next_col = MF_WAVES;  // (the first MF_WAVES columns: one per wave)
   }
   __syncthreads();
   const long S = (long)Ny * Nx;
@@ -766,16 +759,18 @@ __global__ __launch_bounds__(64 * MF_WAVES, 1) void spectral_mfma2_kernel(
   const int zc0 = blockIdx.y * zchunk, zc1 = min(Nz, zc0 + zchunk);
 #ifdef SM_TIMING
   const bool sm_rec = blockIdx.x >= 3 && blockIdx.x < 7 && blockIdx.y == 1 && lane == 0;
-  long long sm_ncol = 0;
   long long sm_wall0 = 0;
   if (sm_rec) {
-    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 4 + 0] = clock64();
+    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 3 + 0] = clock64();
     sm_wall0 = wall_clock64();   // (the constant 100 MHz counter: the ratio gives the shader clock)
   }
 #endif
-  for (int col = wv; col < cols_per_block;) {
+  // (written as a grid-stride loop over the columns: the launch gives every column its own wave, so a
+  // second pass finds nothing and leaves.  As straight-line code with an early return hipcc hoists
+  // more out of the tile loops and the f16-split FOLD variants spill 88 to 152 bytes instead of 60:
+  // profiles/glr_driver_split.txt)
+  for (long w_col = (long)blockIdx.x * MF_WAVES + wv;; w_col += (long)gridDim.x * MF_WAVES) {
   long s_end = s_end_launch;
-  const long w_col = (long)blockIdx.x * cols_per_block + col;
   long s_base = s_first + w_col * 32;
   bool have = true;
   if (rx1 > 0) {
@@ -785,7 +780,7 @@ __global__ __launch_bounds__(64 * MF_WAVES, 1) void spectral_mfma2_kernel(
     s_base = row * Nx + rx0 + 32 * (int)(w_col % wpr);
     s_end = row * Nx + rx1;
   }
-  if (!have || s_base >= s_end) break;  // (columns are handed out in order: nothing behind this one)
+  if (!have || s_base >= s_end) break;
   // A rows: lane r is output channel zi = r & 15 of the pair's profile r >> 4; its fragment of
   // window block b starts at G[31 - zi + 8 h + 16 b]
   const int E0 = 8 * h - (r & 15) + 31;
@@ -843,19 +838,11 @@ __global__ __launch_bounds__(64 * MF_WAVES, 1) void spectral_mfma2_kernel(
       part_min[(long)blockIdx.y * S + sc] = b;
     }
   }
-  // the next column nobody has taken yet (lane 0 asks, the wave follows)
-  int nxt = 0;
-  if (lane == 0) nxt = atomicAdd(&sm_next_col, 1);
-  col = __builtin_amdgcn_readfirstlane(nxt);
-#ifdef SM_TIMING
-  ++sm_ncol;
-#endif
-  }  // columns of this block
+  }  // columns
 #ifdef SM_TIMING
   if (sm_rec) {
-    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 4 + 1] = clock64();
-    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 4 + 2] = sm_ncol;
-    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 4 + 3] = wall_clock64() - sm_wall0;
+    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 3 + 1] = clock64();
+    sm_wave[((blockIdx.x - 3) * MF_WAVES + wv) * 3 + 2] = wall_clock64() - sm_wall0;
   }
 #endif
 }
@@ -915,50 +902,36 @@ long origin_spectral_mfma_count(int num_cu, int terms, int K, int n_narrow, int 
 }
 
 // Launch: a wave = 32 spaxels x 32-channel tiles (two 16-channel halves); z chunks sized to give every CU several blocks
-// (one block per CU at a time: K * (4.5 KiB + MF_WAVES * 128 B) of LDS).  Returns the number of z
-// chunks (rows of part_max / part_min) in *nzc.  nN: number of narrow profiles (the first nN
-// slots of the processing order).
-int origin_spectral_mfma_launch(origin_ctx *ctx, int terms, const float *fsf, const float *rden,
-                                const float *rdi_s, int NzP, const uint4 *atab, const int *pinfo,
-                                int K, int nN, int Nz, int Ny, int Nx, int P, const uint8_t *mask,
-                                float *correl, uint8_t *profile, float *correl_min, float *part,
-                                bool want_maps, int *nzc_out, float **pmax_out, float **pmin_out,
-                                const uint4 *atab_fold, const float *rden_fold, const float *sden,
-                                int ident, long s_first, long s_count, const float *normc,
-                                int part_rows, int rx0, int rx1) {
-  const long S = (long)Ny * Nx;
+// (one block per CU at a time: K * (4.5 KiB + MF_WAVES * 128 B) of LDS).  Reports the number of z
+// chunks (rows of pmax / pmin) in a.io.
+int origin_spectral_mfma_launch(origin_ctx *ctx, const SpectralMfmaArgs &a) {
+  GlrSpectralIO *io = a.io;
+  const int K = a.K, Nz = a.Nz, Nx = a.Nx;
+  const long S = (long)a.Ny * Nx;
   long bx;
   int nzm, zcm;
   // (the z chunks are those of a launch over the whole field, whatever part of it this one takes:
   // the partial maps of all parts of a run share their layout)
   sm_geometry(ctx->num_cu, Nz, S, &bx, &nzm, &zcm);
+  long s_first = a.s_first, s_count = a.s_count;
   if (s_count <= 0) s_first = 0, s_count = S;
-  if ((rx1 <= 0 && s_first % 32 != 0) || s_first < 0 || s_first + s_count > S) {
+  if ((a.rx1 <= 0 && s_first % 32 != 0) || s_first < 0 || s_first + s_count > S) {
     origin_set_error("spectral MFMA kernel: bad spaxel range");
     return ORIGIN_E_ARG;
   }
-  // columns (32 spaxels x one z chunk) per block: MF_WAVES x SM_COLS_FACTOR, pulled by the waves
-  // (measured at 3681 x 600 x 600 with 1 / 2 / 3 / 4 / 6 columns per wave: 9.59 / 9.80 / 9.72 / 9.80 /
-  // 11.1 ms -- evening out the waves does not move the kernel: while a SIMD's first wave is gone
-  // the other two run that much faster.  One column per wave, as in rounds 2-3, stays the default)
-  static const int cols_factor = getenv("ORIGIN_GLR_SPECTRAL_COLS") ? std::max(1, atoi(getenv("ORIGIN_GLR_SPECTRAL_COLS"))) : 1;
-  int cols_per_block = MF_WAVES * cols_factor;
-  long ncols = cdiv(s_count, 32);
+  long ncols = cdiv(s_count, 32);  // columns (32 spaxels x one z chunk): one per wave
   long s_end = s_first + s_count;
-  if (rx1 > 0) {  // rectangle: whole rows s_first / Nx .. , columns rx0 .. rx1 - 1
-    if (s_first % Nx != 0 || s_count % Nx != 0 || rx0 < 0 || rx0 >= rx1 || rx1 > Nx) {
+  if (a.rx1 > 0) {  // rectangle: whole rows s_first / Nx .. , columns rx0 .. rx1 - 1
+    if (s_first % Nx != 0 || s_count % Nx != 0 || a.rx0 < 0 || a.rx0 >= a.rx1 || a.rx1 > Nx) {
       origin_set_error("spectral MFMA kernel: bad rectangle");
       return ORIGIN_E_ARG;
     }
-    ncols = (s_count / Nx) * (long)cdiv(rx1 - rx0, 32);
+    ncols = (s_count / Nx) * (long)cdiv(a.rx1 - a.rx0, 32);
   }
-  // (small launches -- narrow row bands, rectangles: keep every CU busy before sharing columns)
-  while (cols_per_block > MF_WAVES && cdiv(ncols, cols_per_block) * (long)nzm < 2L * ctx->num_cu)
-    cols_per_block -= MF_WAVES;
-  bx = cdiv(ncols, cols_per_block);
+  bx = cdiv(ncols, MF_WAVES);
   // (part_rows: rows of each partial map when other launches add theirs behind this one's)
-  float *pmax = want_maps ? part : nullptr;
-  float *pmin = want_maps ? part + (size_t)std::max(nzm, part_rows) * S : nullptr;
+  float *pmax = io->want_maps ? io->part : nullptr;
+  float *pmin = io->want_maps ? io->part + (size_t)std::max(nzm, a.part_rows) * S : nullptr;
   const int Kp = K + (K & 1);
   // (+ one profile of slack: the last stage requests the fragments of a pair that is not there)
   const size_t lds = std::max((size_t)Kp * MF_PROF_BYTES + (size_t)K * MF_WAVES * MF_RD_BYTES,
@@ -966,9 +939,9 @@ int origin_spectral_mfma_launch(origin_ctx *ctx, int terms, const float *fsf, co
   // pairs of slots (2p, 2p+1); an odd last profile pairs with itself
   const int NP = (K + 1) / 2;
   auto pick = [&](int fold) -> const void * {
-    const int variant = (NP & 1) | (fold << 1) | ((fold && ident) << 2) | ((fold && normc) << 3);
+    const int variant = (NP & 1) | (fold << 1) | ((fold && a.ident) << 2) | ((fold && a.normc) << 3);
 #define SM_PICK(T, V) \
-  if (terms == T && variant == V) return (const void *)spectral_mfma2_kernel<T, V>
+  if (a.terms == T && variant == V) return (const void *)spectral_mfma2_kernel<T, V>
     SM_PICK(3, 0); SM_PICK(3, 1); SM_PICK(3, 2); SM_PICK(3, 3); SM_PICK(3, 6); SM_PICK(3, 7);
     SM_PICK(1, 0); SM_PICK(1, 1); SM_PICK(1, 2); SM_PICK(1, 3); SM_PICK(1, 6); SM_PICK(1, 7);
     SM_PICK(3, 10); SM_PICK(3, 11); SM_PICK(3, 14); SM_PICK(3, 15);
@@ -979,37 +952,41 @@ int origin_spectral_mfma_launch(origin_ctx *ctx, int terms, const float *fsf, co
   // FOLD for the tiles whose profile supports lie inside the cube (plans whose eps test passed
   // bring the folded tables), the exact form for the tiles at the ends
   int zf0 = 0, zf1 = 0;
-  if (atab_fold && ((rden_fold && sden) || normc) && !getenv("ORIGIN_GLR_NO_FOLD")) {
-    mf_fold_range(Nz, &zf0, &zf1);
-  }
+  if (a.atab_fold && ((a.rden_fold && a.sden) || a.normc)) mf_fold_range(Nz, &zf0, &zf1);
   // (LDS: the tap copies and the staging rows -- K <= 24 with twelve waves)
   const size_t lds_fold = (size_t)Kp * MF_PROF_BYTES + (size_t)MF_WAVES * MF_STAGE_BYTES;
   if (!mf_fold_fits(K) || NP < 2) zf0 = zf1 = 0;  // (the FOLD pair loop peels its first two stages)
   const int fold = zf1 > zf0;
   const void *fn = pick(fold);
   if (!fn) {
-    origin_set_error("spectral MFMA kernel: no variant for %d terms", terms);
+    origin_set_error("spectral MFMA kernel: no variant for %d terms", a.terms);
+    return ORIGIN_E_STATE;
+  }
+  if (a.normc && !fold) {
+    origin_set_error("spectral MFMA kernel: the norm-cube form needs the FOLD range");
     return ORIGIN_E_STATE;
   }
   ORIGIN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  MF_MAX_K * (MF_PROF_BYTES + MF_WAVES * MF_RD_BYTES)));
-  const uint4 *a_atab = fold ? atab_fold : atab;
-  const float *a_rden = fold ? rden_fold : rden;
-  if (fold && normc) sden = normc;  // (NORMW: the kernel's sden argument is the norm cube)
-  if (normc && !fold) {
-    origin_set_error("spectral MFMA kernel: the norm-cube form needs the FOLD range");
-    return ORIGIN_E_STATE;
-  }
-  int a_NP = NP, a_zcm = zcm;
-  void *args[] = {&fsf, &a_rden, &rdi_s, &NzP, &a_atab, &pinfo, &K, &a_NP, &Nz, &Ny, &Nx, &P, &a_zcm,
-                  &mask, &correl, &profile, &correl_min, &pmax, &pmin, &sden, &zf0, &zf1, &nN, &s_first, &s_end, &rx0, &rx1,
-                  &cols_per_block};
+  // the kernel's arguments, in its order
+  const float *fsf = io->fsf, *k_rden = fold ? a.rden_fold : a.rden, *rdi_s = a.rdi_s;
+  const float *k_sden = fold && a.normc ? a.normc : a.sden;  // (NORMW: the norm cube)
+  const uint4 *k_atab = fold ? a.atab_fold : a.atab;
+  const int *pinfo = a.pinfo;
+  const uint8_t *mask = io->mask;
+  float *correl = io->correl, *correl_min = io->correl_min;
+  uint8_t *profile = io->profile;
+  int NzP = a.NzP, k_K = K, k_NP = NP, k_Nz = Nz, Ny = a.Ny, k_Nx = Nx, P = a.P, k_zcm = zcm;
+  int nN = a.n_narrow, rx0 = a.rx0, rx1 = a.rx1;
+  void *args[] = {&fsf, &k_rden, &rdi_s, &NzP, &k_atab, &pinfo, &k_K, &k_NP, &k_Nz, &Ny, &k_Nx, &P,
+                  &k_zcm, &mask, &correl, &profile, &correl_min, &pmax, &pmin, &k_sden, &zf0, &zf1,
+                  &nN, &s_first, &s_end, &rx0, &rx1};
   ORIGIN_HIP(hipLaunchKernel(fn, dim3((unsigned)bx, (unsigned)nzm), dim3(64 * MF_WAVES), args,
                              fold ? std::max(lds, lds_fold) : lds, ctx->stream));
   ORIGIN_LAUNCH_CHECK();
-  *nzc_out = nzm;
-  *pmax_out = pmax;
-  *pmin_out = pmin;
+  io->nzc = nzm;
+  io->pmax = pmax;
+  io->pmin = pmin;
   return ORIGIN_OK;
 }
 
@@ -1018,6 +995,6 @@ extern "C" int origin_debug_sm_timing(long long *out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sm_tim), sizeof(long long) * 8 * MF_WAVES * 8);
 }
 extern "C" int origin_debug_sm_waves(long long *out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sm_wave), sizeof(long long) * 4 * MF_WAVES * 4);
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sm_wave), sizeof(long long) * 4 * MF_WAVES * 3);
 }
 #endif

@@ -459,6 +459,40 @@ def test_glr_weighted_fields_fold_form_on_the_norm_cube(ctx, monkeypatch, precis
         assert np.mean(exact["profile"][:, sel] != ref[1][:, sel]) <= 1e-4
 
 
+def test_glr_weighted_plan_reports_no_eps_before_its_first_run(ctx, monkeypatch):
+    """A plan with a norm cube measures eps of the FOLD form in its first run.  Before that run it
+    reports eps = +inf and FOLD inactive; after it eps is a measured (finite) number and `active`
+    says whether it is within the limit.  Nz = 96 is the smallest cube whose FOLD range [32, 64)
+    is not empty.  Nothing is asserted about the size of eps.  With two profiles (one pair) the
+    spectral stage is the two-product kernel whatever eps says: its results meet the float64 oracle
+    at the bounds test_glr_weighted_fields_on_matrix_cores sets for that kernel on unit noise."""
+    from origin_amd import kernels
+    rng = np.random.default_rng(43)
+    Nz, Ny, Nx, P = 96, 16, 16, 5
+    cube = rng.standard_normal((Nz, Ny, Nx)).astype(np.float32)
+    psfs = [synth.moffat_psf(Nz, P, fwhm0=3.4 - 0.2 * f, fwhm1=3.0 + 0.2 * f).astype(np.float64)
+            for f in range(2)]
+    x = np.linspace(0, 1, Nx)[None, :] * np.ones((Ny, 1))
+    ws = [0.3 + 0.4 * x, 0.7 - 0.4 * x]       # every spaxel is covered: norm > 0 everywhere
+    prof = [np.exp(-0.5 * (np.arange(-lw, lw + 1) / s) ** 2) for lw, s in ((8, 2.5), (4, 1.2))]
+    monkeypatch.delenv("ORIGIN_GLR_NO_FOLD", raising=False)
+    plan = kernels.GLRPlan(ctx, cube.shape, psfs, ws, prof, None, True, precision="f16x2")
+    eps, active = plan.fold_eps()
+    assert eps == np.inf and active is False
+    out = plan.run(ctx.to_device(cube), mask=None, want_maps=True)
+    eps, active = plan.fold_eps()
+    got = {k: out[k].to_host() for k in ("correl", "correl_min", "profile", "maxmap")}
+    plan.close()
+    assert np.isfinite(eps)
+    assert active == (eps <= 2e-6)
+    ref = cpu_ref.Correlation_GLR_test(cube.astype(np.float64), psfs, ws, prof, nthreads=1,
+                                       pcut=None, pmeansub=True)
+    assert np.max(np.abs(got["correl"] - ref[0])) <= 1e-4
+    assert np.max(np.abs(got["correl_min"] - ref[2])) <= 1e-4
+    assert np.mean(got["profile"] != ref[1]) <= 1e-4
+    assert np.max(np.abs(got["maxmap"] - ref[0].max(axis=0))) <= 1e-4
+
+
 def test_glr_bf16_precision_meets_the_bf16_tolerance(ctx):
     """precision="bf16" (BASELINE config 4): one bf16 MFMA per product in the spectral stage.
     SURVEY 8c tolerance for bf16 operands with wide accumulation: |dT| <= 5e-2, rms <= 5e-3,

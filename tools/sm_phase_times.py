@@ -42,21 +42,21 @@ for w in range(NW):
 m = np.median(np.array(allr), axis=0)
 print("median over waves and tiles:", " ".join(f"{n}={int(v)}" for n, v in zip(names + ["tile"], m)))
 print("a tile is 240 MFMAs = 7 680 matrix-pipe cycles per wave, three waves per SIMD")
-wb = (C.c_longlong * (4 * NW * 4))()
+wb = (C.c_longlong * (4 * NW * 3))()
 lib.origin_debug_sm_waves.argtypes = [C.c_void_p]
 print("rc", lib.origin_debug_sm_waves(wb))
-wt = np.array(wb[:], dtype=np.int64).reshape(4, NW, 4)
+wt = np.array(wb[:], dtype=np.int64).reshape(4, NW, 3)
 for b in range(4):
     t0 = wt[b, :, 0].min()
-    print(f"block {b + 3}: wave (start, end, columns) relative to the block's first wave:")
-    print("   " + "  ".join(f"w{w}:{int(wt[b, w, 0] - t0)}-{int(wt[b, w, 1] - t0)}/{int(wt[b, w, 2])}" for w in range(NW)))
+    print(f"block {b + 3}: wave (start, end) relative to the block's first wave:")
+    print("   " + "  ".join(f"w{w}:{int(wt[b, w, 0] - t0)}-{int(wt[b, w, 1] - t0)}" for w in range(NW)))
     print(f"   block lifetime {int(wt[b, :, 1].max() - t0)}, sum of wave lifetimes / (12 x lifetime) = "
           f"{float((wt[b, :, 1] - wt[b, :, 0]).sum()) / (NW * float(wt[b, :, 1].max() - t0)):.2f}")
     dt_ticks = (wt[b, :, 1] - wt[b, :, 0]).astype(float)
-    dt_wall = wt[b, :, 3].astype(float)          # 100 MHz ticks
+    dt_wall = wt[b, :, 2].astype(float)          # 100 MHz ticks
     ok = dt_wall > 0
     if ok.any():
         mhz = dt_ticks[ok] / dt_wall[ok] * 100.0
         print(f"   clock64 ticks per microsecond over the waves' lifetimes: {mhz.min():.0f} .. {mhz.max():.0f} "
               f"(clock64 against the 100 MHz wall clock: the shader clock in MHz if clock64 counts shader cycles); "
-              f"block lifetime {float(wt[b, :, 3].max()) / 100.0:.1f} us")
+              f"block lifetime {float(wt[b, :, 2].max()) / 100.0:.1f} us")
