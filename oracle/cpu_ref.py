@@ -73,6 +73,57 @@ def dct_residual(w_raw, order, var, approx, mask):
     return np.stack(cont).T.reshape(w_raw.shape)
 
 
+def dct_fit_columns(raw, var, mask, order, approx=False, weights=None):
+    """``dct_residual`` of the columns of (Nz, n) arrays, vectorised (batched float64 solve), for
+    samples of fields too large for the per-spaxel loop above.
+
+    Returns (cont, coef): the (Nz, n) continuum and the (order+1, n) coefficients of the
+    UNNORMALISED cosine atoms, cont[z] = sum_a coef[a] cos(a theta_z), theta_z = (z + 1/2) pi / Nz
+    (the convention of csrc/dct.hip: the s_a sqrt(2/Nz) of DCTMAT cancel in D (D^T W D)^-1 D^T W).
+    A column with a masked voxel, and every column under ``approx``, takes D0 D0^T s, i.e.
+    coef_0 = R0_0 / Nz, coef_a = 2 R0_a / Nz with R0 = C^T s (:191-194, :237); the others the
+    weighted LSQ (:233-235).  ``weights``: (Nz, n) array used instead of 1 / var.
+    """
+    raw = np.asarray(raw, dtype=np.float64)
+    mask = np.asarray(mask, dtype=bool)
+    nl, n = raw.shape
+    na = order + 1
+    C = np.cos(((np.arange(nl) + 0.5) * (np.pi / nl))[:, None] * np.arange(na))
+    scale = np.full(na, 2.0 / nl)
+    scale[0] = 1.0 / nl
+    coef = (C.T @ raw) * scale[:, None]
+    if not approx:
+        valid = np.flatnonzero(~mask.any(axis=0))
+        if valid.size:
+            with np.errstate(divide="ignore"):
+                w = (1.0 / np.asarray(var, dtype=np.float64)[:, valid] if weights is None
+                     else np.asarray(weights, dtype=np.float64)[:, valid])
+            CC = (C[:, :, None] * C[:, None, :]).reshape(nl, na * na)
+            G = (CC.T @ w).T.reshape(-1, na, na)          # C^T W C of every column
+            rhs = (C.T @ (w * raw[:, valid])).T           # C^T W s
+            coef[:, valid] = np.linalg.solve(G, rhs[:, :, None])[:, :, 0].T
+    return C @ coef, coef
+
+
+def standardize_columns(raw, var, mask, cont, zmean, inv_std=None):
+    """The lines of ``preprocessing`` below that follow the fit, on (Nz, n) columns of a cube whose
+    per-channel means ``zmean`` (the nanmean of steps.py:442, over the WHOLE field) are given, so
+    that a sample of columns suffices.  ``inv_std``: used instead of 1 / sqrt(var).
+    Returns dict(cube_std, cont_dct (float32), ima_std, ima_dct, o2) of those columns.
+    """
+    raw = np.asarray(raw, dtype=np.float64)
+    mask = np.asarray(mask, dtype=bool)
+    if inv_std is None:
+        with np.errstate(divide="ignore"):
+            inv_std = 1.0 / np.sqrt(np.asarray(var, dtype=np.float64))   # steps.py:439
+    with np.errstate(invalid="ignore"):
+        data = ((raw - cont) - np.asarray(zmean, dtype=np.float64)[:, None]) * inv_std  # :434-445
+    data[mask] = 0                                                       # :446
+    cont32 = (cont * inv_std).astype(np.float32)                         # :440, :463
+    return dict(cube_std=data, cont_dct=cont32, ima_std=data.mean(axis=0),
+                ima_dct=cont32.mean(axis=0, dtype=np.float64), o2=np.mean(data ** 2, axis=0))
+
+
 def preprocessing(cube_raw, var, mask, dct_order=10, dct_approx=False):
     """Dense part of ``Preprocessing.run`` (steps.py:431-450, :463-465).
 

@@ -171,3 +171,67 @@ def test_step7_merging_of_std_detections():
     np.testing.assert_array_equal(cat0["STD"], [np.nan, np.nan, 6.0, 5.0])
     np.testing.assert_array_equal(cat0["profile"], [prof[0, 2, 4], prof[2, 1, 3], 0, 0])
     np.testing.assert_array_equal(keep, [0])                          # (0,0,0) survives
+
+
+def _close(a, b, tol):
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    assert a.shape == b.shape
+    assert np.max(np.abs(a - b)) <= tol * max(np.max(np.abs(b)), 1e-300)
+
+
+def test_column_references_equal_the_per_spaxel_oracle():
+    """cpu_ref.dct_fit_columns / standardize_columns (the vectorised float64 references that
+    tests/test_hip_dct_geometry.py runs on samples of large fields) against the per-spaxel loop of
+    cpu_ref.dct_residual / cpu_ref.preprocessing: a small masked cube of odd and of even Nz at
+    1e-12 relative, and the golden vectors at the tolerances of tests/test_oracle_golden.py."""
+    for Nz, Ny, Nx, order in ((37, 4, 5, 10), (40, 3, 6, 4)):
+        rng = np.random.default_rng(Nz)
+        raw = rng.standard_normal((Nz, Ny, Nx)) * 3 + 50 + 10 * np.linspace(0, 1, Nz)[:, None, None]
+        var = 1.0 + rng.random((Nz, Ny, Nx))
+        mask = rng.random((Nz, Ny, Nx)) < 0.01
+        mask[:, 1, 2] = True                      # a fully masked spaxel
+        mask[Nz // 2, 2, 3] = True                # the middle channel alone
+        raw[mask], var[mask] = 0.0, np.inf
+        S = Ny * Nx
+        cols = [a.reshape(Nz, S) for a in (raw, var, mask)]
+        D0 = cpu_ref.DCTMAT(Nz, order)
+        for approx in (False, True):
+            cont, coef = cpu_ref.dct_fit_columns(*cols, order, approx)
+            _close(cont.reshape(Nz, Ny, Nx), cpu_ref.dct_residual(raw, order, var, approx, mask),
+                   1e-12)
+            # the coefficients are those of the unnormalised cosines: plain-fit columns are
+            # D0^T s rescaled by the atoms' own norms, y_0 = R0_0 / Nz, y_a = 2 R0_a / Nz
+            plain = np.ones(S, bool) if approx else cols[2].any(axis=0)
+            assert plain.any() and (approx or not plain.all())
+            norm = D0[0] / np.cos(0.5 * np.pi / Nz * np.arange(order + 1))
+            _close(coef[:, plain], (D0.T @ cols[0][:, plain]) * norm[:, None], 1e-12)
+            # standardisation of a SAMPLE of columns, given the whole field's channel means
+            ref = cpu_ref.preprocessing(raw.copy(), var.copy(), mask, order, approx)
+            with np.errstate(invalid="ignore"):
+                zmean = np.nanmean(np.where(cols[2], np.nan, cols[0] - cont), axis=1)
+            pick = np.array([0, 7, 1 * Nx + 2, 2 * Nx + 3, S - 1])
+            out = cpu_ref.standardize_columns(cols[0][:, pick], cols[1][:, pick], cols[2][:, pick],
+                                              cont[:, pick], zmean)
+            full = {k: np.asarray(v).reshape(v.shape[:-2] + (S,))[..., pick] for k, v in ref.items()}
+            _close(out["cube_std"], full["cube_std"], 1e-12)
+            _close(out["ima_std"], full["ima_std"], 1e-12)
+            _close(out["o2"], cpu_ref.O2test(ref["cube_std"]).reshape(S)[pick], 1e-12)
+            _close(out["cont_dct"], full["cont_dct"], 1e-6)
+            _close(out["ima_dct"], full["ima_dct"], 1e-6)
+            assert np.all(out["cube_std"][cols[2][:, pick]] == 0)
+    # the golden vectors recorded from the reference itself
+    inp = gc.g1_inputs()
+    Nz, Ny, Nx = inp["raw"].shape
+    cols = [inp[k].reshape(Nz, -1) for k in ("raw", "var", "mask")]
+    g1 = np.load(os.path.join(gc.GOLDEN_DIR, "g1_dct.npz"))
+    for approx, key, name in ((False, "cont", "g2_preproc"), (True, "cont_approx", "g2_preproc_approx")):
+        cont, _ = cpu_ref.dct_fit_columns(cols[0].astype(float), cols[1].astype(float), cols[2],
+                                          10, approx)
+        _close(cont.reshape(Nz, Ny, Nx), g1[key], 1e-12)
+        g2 = np.load(os.path.join(gc.GOLDEN_DIR, name + ".npz"))
+        with np.errstate(invalid="ignore"):
+            zmean = np.nanmean(np.where(cols[2], np.nan, cols[0].astype(float) - cont), axis=1)
+        out = cpu_ref.standardize_columns(cols[0], cols[1], cols[2], cont, zmean)
+        for k, tol in (("cube_std", 1e-12), ("ima_std", 1e-12), ("o2", 1e-12), ("cont_dct", 1e-6),
+                       ("ima_dct", 1e-6)):
+            _close(out[k].reshape(g2[k].shape), g2[k], tol)
