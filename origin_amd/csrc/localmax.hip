@@ -3,7 +3,6 @@
 // same on -correl_min.  scipy's default border mode 'reflect' duplicates edge samples,
 // which for a maximum is the same as clamping the window to the cube.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 #include "common.h"
 
@@ -40,10 +39,7 @@ __global__ __launch_bounds__(256) void local_max_kernel(const float *__restrict_
 // registers.  No LDS, no barrier: the tile-through-LDS form of round 1 (three block barriers per
 // channel) ran at 2.5 TB/s of algorithmic bytes.  Exact: a maximum does not depend on the order
 // of its operands.
-#ifndef LM_ROWS_N
-#define LM_ROWS_N 4
-#endif
-constexpr int LM_ROWS = LM_ROWS_N;
+constexpr int LM_ROWS = 4;
 // NC = 2: correl (local maxima) and correl_min (local maxima of its negative) in one march: the
 // mask is read once and the index arithmetic is shared.
 template <int NC>
@@ -126,29 +122,13 @@ __device__ __forceinline__ float wave_from_next(float v) {  // lane i gets lane 
                                                     0xF, 0xF, false));  // wave_shl:1
 }
 
-// SPARSE (round 4): the two output cubes are > 98 % zeros (a voxel in ~70 of a smoothed cube is a
-// 3x3x3 maximum), and writing them dense is half of the pass's traffic (17 B per voxel: 9 in, 8
-// out).  The sparse form writes (linear index, value) pairs of the non-zero outputs instead: every
-// wave owns a segment of `seg_cap` entries per cube in idx0 / val0 (maxima of a0) and idx1 / val1
-// (maxima of -a1) and appends to it -- a wave-uniform counter, ballot + mbcnt for the lanes' slots,
-// no atomics, no second pass; the number of entries of wave w ends up in counts[w] (cube 0) and
-// counts[nwaves + w] (cube 1), entries beyond the capacity are counted but not stored (the host
-// sees counts > seg_cap and falls back to the dense form).  9 B per voxel read, ~0.4 B written.
-struct LmSparse {
-  long long *idx0, *idx1;
-  float *val0, *val1;
-  int *counts;
-  int seg_cap;
-};
-
-template <int NC, int R, bool SPARSE = false>
+template <int NC, int R>
 __global__ __launch_bounds__(256) void local_max3v_kernel(const float *__restrict__ a0,
                                                           const float *__restrict__ a1,
                                                           const uint8_t *__restrict__ mask, int Nz,
                                                           int Ny, int Nx, int zper, float sign0,
                                                           float *__restrict__ out0,
-                                                          float *__restrict__ out1,
-                                                          LmSparse sp = LmSparse()) {
+                                                          float *__restrict__ out1) {
   // Waves overlap by two lanes: wave w holds the flattened (row group, float4 column) indices
   // 62 w - 1 .. 62 w + 62; lanes 1..62 produce outputs, lanes 0 and 63 only hand their samples to
   // their neighbours -- no lane ever loads a halo sample (a conditional 4-byte load per row and
@@ -204,18 +184,9 @@ __global__ __launch_bounds__(256) void local_max3v_kernel(const float *__restric
     plane(a1, -1.0f, z0 - 1, pa[1], dummy);
     plane(a1, -1.0f, z0, pb[1], cb[1]);
   }
-  // sparse form: this wave's segments and how many entries they hold so far (wave-uniform)
-  const long wave_id = ((long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6);
-  const long seg = SPARSE ? wave_id * sp.seg_cap : 0;
-  int cnt[NC];
-#pragma unroll
-  for (int q = 0; q < NC; ++q) cnt[q] = 0;
   for (int z = z0; z < z1; ++z) {
     plane(a0, sign0, z + 1, pc[0], cc[0]);
     if constexpr (NC == 2) plane(a1, -1.0f, z + 1, pc[1], cc[1]);
-    unsigned km[NC];   // SPARSE: bit 4 r + e = output (r, e) of this lane is a non-zero maximum
-#pragma unroll
-    for (int q = 0; q < NC; ++q) km[q] = 0u;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int y = yb + r;
@@ -231,13 +202,10 @@ __global__ __launch_bounds__(256) void local_max3v_kernel(const float *__restric
             const bool unmasked = ((mk >> (8 * e)) & 0xffu) == 0u;
             const bool keep = cb[q][r][e] == m && unmasked;     // local_max *= local_mask (lib :1247)
             o[q][e] = keep ? m : 0.0f;
-            if constexpr (SPARSE) km[q] |= (keep && m != 0.0f) ? (1u << (4 * r + e)) : 0u;
           }
-        if constexpr (!SPARSE) {
-          *reinterpret_cast<float4 *>(out0 + idx) = make_float4(o[0][0], o[0][1], o[0][2], o[0][3]);
-          if constexpr (NC == 2)
-            *reinterpret_cast<float4 *>(out1 + idx) = make_float4(o[1][0], o[1][1], o[1][2], o[1][3]);
-        }
+        *reinterpret_cast<float4 *>(out0 + idx) = make_float4(o[0][0], o[0][1], o[0][2], o[0][3]);
+        if constexpr (NC == 2)
+          *reinterpret_cast<float4 *>(out1 + idx) = make_float4(o[1][0], o[1][1], o[1][2], o[1][3]);
       }
 #pragma unroll
       for (int q = 0; q < NC; ++q)
@@ -245,53 +213,30 @@ __global__ __launch_bounds__(256) void local_max3v_kernel(const float *__restric
         for (int e = 0; e < 4; ++e)
           pa[q][r][e] = pb[q][r][e], pb[q][r][e] = pc[q][r][e], cb[q][r][e] = cc[q][r][e];
     }
-    if constexpr (SPARSE) {
-      // append the lanes' maxima of this channel to the wave's segments: one round per entry of
-      // the busiest lane (usually one or two); the value is read back from the cube (the line is
-      // in cache: this lane loaded it a channel ago)
-      const long zbase = (long)z * S + (long)yb * Nx + 4 * x4;
-#pragma unroll
-      for (int q = 0; q < NC; ++q) {
-        unsigned m = km[q];
-        const float *src = q == 0 ? a0 : a1;
-        const float sg = q == 0 ? sign0 : -1.0f;
-        long long *ix = q == 0 ? sp.idx0 : sp.idx1;
-        float *vl = q == 0 ? sp.val0 : sp.val1;
-        for (;;) {
-          const unsigned long long bal = __ballot(m != 0u);
-          if (bal == 0ull) break;
-          if (m != 0u) {
-            const int b = __builtin_ctz(m);
-            m &= m - 1u;
-            const long at = zbase + (long)(b >> 2) * Nx + (b & 3);
-            const int slot = cnt[q] + (int)__builtin_amdgcn_mbcnt_hi(
-                                          (unsigned)(bal >> 32),
-                                          __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-            if (slot < sp.seg_cap) {
-              ix[seg + slot] = at;
-              vl[seg + slot] = sg * src[at];
-            }
-          }
-          cnt[q] += __popcll(bal);
-        }
-      }
-    }
-  }
-  if constexpr (SPARSE) {
-    if (lane == 0) {
-      const long nwaves = (long)gridDim.x * gridDim.y * 4;
-#pragma unroll
-      for (int q = 0; q < NC; ++q) sp.counts[q * nwaves + wave_id] = cnt[q];
-    }
   }
 }
 
-// ---- the sparse pass, second form (round 4) ------------------------------------------------
-// The kernel above, compiled with SPARSE, takes 4.05 ms at 3681 x 600 x 600 against 4.6 ms for the
-// dense cubes: not the bytes (9 B per voxel: 2.9 TB/s) but ~770 instructions per wave and channel
-// -- sign multiplies, canonicalising maxima, 115 register moves that rotate the three planes,
-// per-output compare / select / bit-merge chains -- on two waves per SIMD.  This form does the same
-// arithmetic in ~100 VALU instructions per wave and channel:
+// ---- the sparse pass (round 4) -------------------------------------------------------------
+// The two output cubes are > 98 % zeros (a voxel in ~70 of a smoothed cube is a 3x3x3 maximum), and
+// writing them dense is half of the pass's traffic (17 B per voxel: 9 in, 8 out).  The sparse form
+// writes (linear index, value) pairs of the non-zero outputs instead: every wave owns a segment of
+// `seg_cap` entries per cube in idx0 / val0 (maxima of a0) and idx1 / val1 (maxima of -a1) and
+// appends to it -- a wave-uniform counter, ballot + mbcnt for the lanes' slots, no atomics, no
+// second pass; the number of entries of wave w ends up in counts[w] (cube 0) and
+// counts[nwaves + w] (cube 1), entries beyond the capacity are counted but not stored (the host
+// sees counts > seg_cap and falls back to the dense form).  9 B per voxel read, ~0.4 B written.
+struct LmSparse {
+  long long *idx0, *idx1;
+  float *val0, *val1;
+  int *counts;
+  int seg_cap;
+};
+
+// The dense kernel above made to append (the first sparse form) took 4.05 ms at 3681 x 600 x 600
+// against 4.6 ms for the dense cubes: not the bytes (9 B per voxel: 2.9 TB/s) but ~770 instructions
+// per wave and channel -- sign multiplies, canonicalising maxima, 115 register moves that rotate the
+// three planes, per-output compare / select / bit-merge chains -- on two waves per SIMD.  This form
+// does the same arithmetic in ~100 VALU instructions per wave and channel:
 //   * one cube per wave (grid z = cube): half the registers, four or more waves per SIMD; the
 //     minima of correl_min are found as minima (v_min3), not as maxima of a negated copy;
 //   * the three planes rotate by NAME (the channel loop is unrolled by three), no moves;
@@ -314,24 +259,16 @@ struct LmPlane {
   float c[R][NC];  // the plane's own samples there
 };
 
-// NC consecutive samples of a row as one load (16 / 8 / 4 bytes per lane)
-template <int NC>
-__device__ __forceinline__ void lm_load_row(const char *p, float (&v)[NC]) {
-  if constexpr (NC == 4) {
-    const float4 q = *reinterpret_cast<const float4 *>(p);
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  } else if constexpr (NC == 2) {
-    const float2 q = *reinterpret_cast<const float2 *>(p);
-    v[0] = q.x, v[1] = q.y;
-  } else {
-    v[0] = *reinterpret_cast<const float *>(p);
-  }
+// two consecutive samples of a row as one 8-byte load
+__device__ __forceinline__ void lm_load_row(const char *p, float (&v)[2]) {
+  const float2 q = *reinterpret_cast<const float2 *>(p);
+  v[0] = q.x, v[1] = q.y;
 }
 
 // NC: samples per lane and row (a wave's row segment is 64 NC samples, 62 NC of them outputs); R rows
 // per lane: R + 2 rows are read for R rows of outputs, so the same register budget (R NC outputs per
 // lane) spent on fewer columns and more rows reads less twice.
-template <int SIGN, int R, int NC, bool HAS_MASK, bool PREFETCH, bool STRIPS>
+template <int SIGN, int R, int NC, bool HAS_MASK>
 __device__ __forceinline__ void lm_sparse_march(const float *__restrict__ a,
                                                 const uint8_t *__restrict__ mask, int Nz, int Ny,
                                                 int Nx, int zper, long long *__restrict__ idx_out,
@@ -341,36 +278,18 @@ __device__ __forceinline__ void lm_sparse_march(const float *__restrict__ a,
   // (bxi, bzi: this block's position among the nbx spaxel blocks and the z chunks)
   const int nx4 = Nx / NC, ngrp = (Ny + R - 1) / R;   // (nx4: lane positions per row)
   const int lane = threadIdx.x & 63;
-  bool live;
-  int grp, x4;
-  if constexpr (STRIPS) {
-    // The four waves of a block take four row groups ONE ABOVE THE OTHER (a strip of 4 R rows) at
-    // the same columns: rows yb - 1 and yb + R of a wave are own rows of its siblings, loaded on the
-    // same CU within the same channel step -- they meet in the CU's L1 / the XCD's L2 instead of
-    // coming from memory twice (the counter passes of the flattened mapping below: 13.9 B per voxel
-    // fetched for 8 read, profiles/r04_pmc_fetch_write.json).  Only a strip's outer two rows are
-    // shared with other blocks: (4 R + 2) / 4 R = 1.125 instead of (R + 2) / R = 1.5 row fetches.
-    // Price: a row is cut into chunks of 62 producing lanes, the last one partly empty.
-    const int nxc = (nx4 + 61) / 62;
-    const int sb = (int)(bxi / nxc), xc = (int)(bxi - (long)sb * nxc);
-    grp = min(4 * sb + (int)(threadIdx.x >> 6), ngrp - 1);
-    const int x_raw = 62 * xc - 1 + lane;
-    live = lane >= 1 && lane <= 62 && x_raw < nx4 && 4 * sb + (int)(threadIdx.x >> 6) < ngrp;
-    x4 = min(max(x_raw, 0), nx4 - 1);
-  } else {
-    const long total = (long)ngrp * nx4;
-    const long wv = bxi * 4 + (threadIdx.x >> 6);
-    const long t_raw = 62 * wv - 1 + lane;
-    live = lane >= 1 && lane <= 62 && t_raw < total;
-    const long t = min(max(t_raw, 0L), total - 1);
-    grp = (int)(t / nx4);
-    x4 = (int)(t - (long)grp * nx4);
-  }
+  const long total = (long)ngrp * nx4;
+  const long wv = bxi * 4 + (threadIdx.x >> 6);
+  const long t_raw = 62 * wv - 1 + lane;
+  const bool live = lane >= 1 && lane <= 62 && t_raw < total;
+  const long t = min(max(t_raw, 0L), total - 1);
+  const int grp = (int)(t / nx4);
+  const int x4 = (int)(t - (long)grp * nx4);
   const int yb = grp * R;
   const int z0 = bzi * zper, z1 = min(Nz, z0 + zper);
   const long S = (long)Ny * Nx;
   const bool first = x4 == 0, last = x4 == nx4 - 1;
-  unsigned roff[R + 2];  // byte offsets of rows yb - 1 .. yb + R (clamped) at this lane's float4
+  unsigned roff[R + 2];  // byte offsets of rows yb - 1 .. yb + R (clamped) at this lane's samples
 #pragma unroll
   for (int r = 0; r < R + 2; ++r)
     roff[r] = 4u * (unsigned)((long)min(max(yb - 1 + r, 0), Ny - 1) * Nx + NC * x4);
@@ -389,21 +308,12 @@ __device__ __forceinline__ void lm_sparse_march(const float *__restrict__ a,
       // 32-bit lane offset" is one addressing mode; hoisted, each row costs a 64-bit VGPR pair)
       unsigned o = roff[r];
       asm volatile("" : "+v"(o));
-      lm_load_row<NC>(pz + o, v[r]);
+      lm_load_row(pz + o, v[r]);
     }
   };
-  float vnext[R + 2][NC];   // PREFETCH: the rows of the plane after next, requested a channel ahead
   auto plane = [&](int z, LmPlane<R, NC> &o) {
     float v[R + 2][NC];
-    if constexpr (PREFETCH) {
-#pragma unroll
-      for (int r = 0; r < R + 2; ++r)
-#pragma unroll
-        for (int e = 0; e < NC; ++e) v[r][e] = vnext[r][e];
-      fetch(z + 1, vnext);
-    } else {
-      fetch(z, v);
-    }
+    fetch(z, v);
     float xm[R + 2][NC];
 #pragma unroll
     for (int r = 0; r < R + 2; ++r) {
@@ -466,7 +376,6 @@ __device__ __forceinline__ void lm_sparse_march(const float *__restrict__ a,
       }
   };
   LmPlane<R, NC> A, B, C;
-  if constexpr (PREFETCH) fetch(z0 - 1, vnext);
   plane(z0 - 1, A);
   plane(z0, B);
   int z = z0;
@@ -482,54 +391,32 @@ __device__ __forceinline__ void lm_sparse_march(const float *__restrict__ a,
   if (lane == 0) counts[wave_id] = cnt;
 }
 
-#ifndef LMS_R_N
-#define LMS_R_N 4
-#endif
-#ifndef LMS_NC_N
-#define LMS_NC_N 2
-#endif
 // Measured at 3681 x 600 x 600 (tools/localmax_sparse_time.py, R x NC: ms): 4 x 4 (119 VGPRs, four waves
 // per SIMD) 3.76; 8 x 2 (the same registers, 1.25 instead of 1.5 row fetches per row of outputs) 3.76;
 // 6 x 2 3.42; 5 x 2 3.51; 4 x 2 (72 VGPRs, seven waves per SIMD) 3.36; 2 x 4 3.65; 3 x 2 3.76; 4 x 1 3.77;
 // 12 x 2 and 16 x 1 (spills) 5.1 / 4.5.  Rows fetched twice do not show; waves in flight do.
-constexpr int LMS_R = LMS_R_N;    // rows per lane of the sparse pass
-constexpr int LMS_NC = LMS_NC_N;  // samples per lane and row (4, 2 or 1)
-static_assert(LMS_NC == 4 || LMS_NC == 2 || LMS_NC == 1, "samples per lane and row");
-#ifdef LMS_BLOCKS_N
-constexpr int LMS_BLOCKS = LMS_BLOCKS_N;
-#else
-constexpr int LMS_BLOCKS =   // blocks per CU the registers allow
-    LMS_R * LMS_NC <= 8 ? 6 : (LMS_R * LMS_NC <= 16 ? 4 : (LMS_R * LMS_NC <= 24 ? 3 : 2));
-#endif
+constexpr int LMS_R = 4;   // rows per lane of the sparse pass
+constexpr int LMS_NC = 2;  // samples per lane and row
 
-// 1-D grid of nbx * nzc * 2 blocks.  Workgroups go to the 8 XCDs round robin by their id, and a
-// lane's rows yb - 1 and yb + R are the own rows of lanes nx4 = Nx / 4 flattened positions away --
-// two or three waves on, mostly in the NEXT block.  With the natural numbering that block runs on
-// another XCD, behind another L2, and the shared rows come from HBM twice (the dense form's PMC
-// passes: 1.4 x the read bytes).  So the ids are decoded such that an XCD gets a contiguous range
-// of the (cube, z chunk, spaxel block) order: neighbours in that order run on the same XCD at about
-// the same time and find each other's rows in its L2.
-template <bool HAS_MASK, bool PREFETCH, bool STRIPS>
-__global__ __launch_bounds__(256, PREFETCH ? (LMS_BLOCKS > 3 ? 3 : LMS_BLOCKS) : LMS_BLOCKS) void local_max3s_kernel(const float *__restrict__ a0,
-                                                          const float *__restrict__ a1,
-                                                          const uint8_t *__restrict__ mask, int Nz,
-                                                          int Ny, int Nx, int zper, long nbx, int nzc,
-                                                          int xcd_order, LmSparse sp) {
-  const long nb = (long)gridDim.x;
-  const long xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-  const long base = nb >> 3, rem = nb & 7;
-  long logical = xcd * base + (xcd < rem ? xcd : rem) + within;  // (a bijection of [0, nb))
-  if (!xcd_order) logical = blockIdx.x;
+// 1-D grid of nbx * nzc * 2 blocks in (cube, z chunk, spaxel block) order.  The launch bound of six
+// blocks per CU is the one R x NC = 8 outputs per lane were tuned with.
+template <bool HAS_MASK>
+__global__ __launch_bounds__(256, 6) void local_max3s_kernel(const float *__restrict__ a0,
+                                                             const float *__restrict__ a1,
+                                                             const uint8_t *__restrict__ mask,
+                                                             int Nz, int Ny, int Nx, int zper,
+                                                             long nbx, int nzc, LmSparse sp) {
+  const long logical = blockIdx.x;
   const long bxi = logical % nbx;
   const long t = logical / nbx;
   const int bzi = (int)(t % nzc), cube = (int)(t / nzc);
   const long nwaves = nbx * nzc * 4;
   if (cube == 0)
-    lm_sparse_march<1, LMS_R, LMS_NC, HAS_MASK, PREFETCH, STRIPS>(a0, mask, Nz, Ny, Nx, zper, sp.idx0, sp.val0, sp.counts,
-                                        sp.seg_cap, bxi, bzi, nbx);
+    lm_sparse_march<1, LMS_R, LMS_NC, HAS_MASK>(a0, mask, Nz, Ny, Nx, zper, sp.idx0, sp.val0,
+                                                sp.counts, sp.seg_cap, bxi, bzi, nbx);
   else
-    lm_sparse_march<-1, LMS_R, LMS_NC, HAS_MASK, PREFETCH, STRIPS>(a1, mask, Nz, Ny, Nx, zper, sp.idx1, sp.val1,
-                                         sp.counts + nwaves, sp.seg_cap, bxi, bzi, nbx);
+    lm_sparse_march<-1, LMS_R, LMS_NC, HAS_MASK>(a1, mask, Nz, Ny, Nx, zper, sp.idx1, sp.val1,
+                                                 sp.counts + nwaves, sp.seg_cap, bxi, bzi, nbx);
 }
 
 // ---- consumers of the sparse form ------------------------------------------------------------
@@ -613,6 +500,26 @@ __global__ __launch_bounds__(256) void sparse_zmax_kernel(const long long *__res
   }
 }
 
+struct LmGeom {
+  long bx;  // blocks of four waves over the flattened (row group, column) index
+  int zp;   // channels per z chunk
+  int nzc;  // z chunks
+};
+
+// The launch geometry of the marches whose lanes own R rows x NC samples (local_max3v_kernel,
+// local_max3s_kernel): 62 producing lanes per wave, four waves per block, and z cut into chunks of
+// at least 32 channels until there are ~16 blocks per CU.
+LmGeom lm_geometry(const origin_ctx *ctx, int Nz, int Ny, int Nx, int R, int NC) {
+  const long threads = (long)cdiv(Ny, R) * (Nx / NC);
+  LmGeom g;
+  g.bx = (threads + 4 * 62 - 1) / (4 * 62);
+  int nzc = (int)(((long)ctx->num_cu * 16 + g.bx - 1) / g.bx);
+  nzc = nzc < 1 ? 1 : (nzc > cdiv(Nz, 32) ? cdiv(Nz, 32) : nzc);
+  g.zp = cdiv(Nz, nzc);
+  g.nzc = cdiv(Nz, g.zp);
+  return g;
+}
+
 }  // namespace
 
 extern "C" int origin_local_max(origin_ctx *ctx, const float *d_correl,
@@ -624,52 +531,42 @@ extern "C" int origin_local_max(origin_ctx *ctx, const float *d_correl,
   ORIGIN_CHECK_ARG(Nz <= 65535, "Nz too large for the launch grid");
   // scipy maximum_filter: window offsets  -(size//2) .. size-1-(size//2)
   const int lo = size / 2, hi = size - 1 - size / 2;
-  dim3 grid(cdiv(Nx, 64), cdiv(Ny, 4), Nz), block(64, 4);
+  const dim3 block(64, 4);
+  const bool both = d_correl && d_local_max && d_correl_min && d_local_min;
   ProfScope ps(ctx, K_LOCAL_MAX);
   if (size == 3) {  // the reference's default (steps.py:453, :796)
-    const long tiles = (long)cdiv(Nx, 64) * cdiv(Ny, 4 * LM_ROWS);
-    int nzb = (int)(((long)ctx->num_cu * 32 + tiles - 1) / tiles);  // ~32 blocks per CU
-    nzb = nzb < 1 ? 1 : (nzb > Nz ? Nz : nzb);
-    const int zper = cdiv(Nz, nzb);
-    dim3 g3(cdiv(Nx, 64), cdiv(Ny, 4 * LM_ROWS), cdiv(Nz, zper));
     auto al16 = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
     const bool vec = (Nx & 3) == 0 && al16(d_correl) && al16(d_correl_min) && al16(d_local_max) &&
-                     al16(d_local_min) && ((uintptr_t)d_mask & 3) == 0 && !getenv("ORIGIN_LOCALMAX_SCALAR");
+                     al16(d_local_min) && ((uintptr_t)d_mask & 3) == 0;
     if (vec) {
-      // ORIGIN_LOCALMAX_FORM: 2 = both cubes in one march, four rows per lane (default: 234
-      // VGPRs, two waves per SIMD); 0 = both cubes, two rows per lane; 1 = one march per cube,
-      // four rows per lane.  Measured at 3681 x 600 x 600 (tools/localmax_time.py): 4.79 / 6.42 /
-      // 5.00 ms against 6.27-6.50 ms for the one-sample form -- the row loads a lane shares with
-      // the row groups above and below (R + 2 rows for R outputs) are what is left: both forms
-      // move ~3.5 TB/s of loads through L2; streaming (non-temporal) stores changed nothing.
-      static const int form = getenv("ORIGIN_LOCALMAX_FORM") ? atoi(getenv("ORIGIN_LOCALMAX_FORM")) : 2;
-      const bool both = d_correl && d_local_max && d_correl_min && d_local_min;
-      auto go = [&](auto kernel, int R, const float *a, const float *b, float sgn, float *oa,
-                    float *ob) {
-        const long threads = (long)cdiv(Ny, R) * (Nx / 4);
-        const long bx = (threads + 4 * 62 - 1) / (4 * 62);  // 62 producing lanes per wave
-        int nzc = (int)(((long)ctx->num_cu * 16 + bx - 1) / bx);  // ~16 blocks per CU
-        nzc = nzc < 1 ? 1 : (nzc > cdiv(Nz, 32) ? cdiv(Nz, 32) : nzc);
-        const int zp = cdiv(Nz, nzc);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)bx, cdiv(Nz, zp)), dim3(256), 0, ctx->stream, a, b,
-                           d_mask, Nz, Ny, Nx, zp, sgn, oa, ob, LmSparse());
+      // Both cubes in one march, four rows per lane (228 VGPRs, two waves per SIMD): 4.79 ms at
+      // 3681 x 600 x 600 (tools/localmax_time.py), against 6.42 with two rows per lane, 5.00 with
+      // one march per cube and 6.27-6.50 for the one-sample form.  One march per cube is what runs
+      // when only one cube is asked for.
+      const LmGeom g = lm_geometry(ctx, Nz, Ny, Nx, 4, 4);
+      auto go = [&](auto kernel, const float *a, const float *b, float sgn, float *oa, float *ob) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)g.bx, g.nzc), dim3(256), 0, ctx->stream, a, b,
+                           d_mask, Nz, Ny, Nx, g.zp, sgn, oa, ob);
       };
-      if (both && form == 0)
-        go(local_max3v_kernel<2, 2>, 2, d_correl, d_correl_min, 1.0f, d_local_max, d_local_min);
-      else if (both && form == 2)
-        go(local_max3v_kernel<2, 4>, 4, d_correl, d_correl_min, 1.0f, d_local_max, d_local_min);
+      if (both)
+        go(local_max3v_kernel<2, 4>, d_correl, d_correl_min, 1.0f, d_local_max, d_local_min);
       else {
         if (d_correl && d_local_max)
-          go(local_max3v_kernel<1, 4>, 4, d_correl, (const float *)nullptr, 1.0f, d_local_max,
+          go(local_max3v_kernel<1, 4>, d_correl, (const float *)nullptr, 1.0f, d_local_max,
              (float *)nullptr);
         if (d_correl_min && d_local_min)
-          go(local_max3v_kernel<1, 4>, 4, d_correl_min, (const float *)nullptr, -1.0f, d_local_min,
+          go(local_max3v_kernel<1, 4>, d_correl_min, (const float *)nullptr, -1.0f, d_local_min,
              (float *)nullptr);
       }
       ORIGIN_LAUNCH_CHECK();
       return ORIGIN_OK;
     }
-    if (d_correl && d_local_max && d_correl_min && d_local_min)
+    const long tiles = (long)cdiv(Nx, 64) * cdiv(Ny, 4 * LM_ROWS);
+    int nzb = (int)(((long)ctx->num_cu * 32 + tiles - 1) / tiles);  // ~32 blocks per CU
+    nzb = nzb < 1 ? 1 : (nzb > Nz ? Nz : nzb);
+    const int zper = cdiv(Nz, nzb);
+    const dim3 g3(cdiv(Nx, 64), cdiv(Ny, 4 * LM_ROWS), cdiv(Nz, zper));
+    if (both)
       hipLaunchKernelGGL(local_max3_kernel<2>, g3, block, 0, ctx->stream, d_correl, d_correl_min,
                          d_mask, Nz, Ny, Nx, zper, 1.0f, d_local_max, d_local_min);
     else if (d_correl && d_local_max)
@@ -683,6 +580,7 @@ extern "C" int origin_local_max(origin_ctx *ctx, const float *d_correl,
     ORIGIN_LAUNCH_CHECK();
     return ORIGIN_OK;
   }
+  const dim3 grid(cdiv(Nx, 64), cdiv(Ny, 4), Nz);
   if (d_correl && d_local_max)
     hipLaunchKernelGGL(local_max_kernel, grid, block, 0, ctx->stream, d_correl, d_mask, Nz, Ny, Nx,
                        lo, hi, 1.0f, d_local_max);
@@ -694,39 +592,6 @@ extern "C" int origin_local_max(origin_ctx *ctx, const float *d_correl,
 }
 
 // ---- sparse form: C ABI ---------------------------------------------------------------------
-namespace {
-
-struct LmGeom {
-  long bx;
-  int zp, nzc;
-};
-
-// ORIGIN_LOCALMAX_STRIPS=1: strips of four row groups per block instead of the flattened (row
-// group, column) mapping.  Measured (tools/localmax_sparse_time.py): 4.16 against 3.77 ms at
-// 3681 x 600 x 600, 9.57 against 8.31 ms at 900 x 900 -- the partly empty last chunk of every row
-// (150 float4 columns = 62 + 62 + 26 lanes) costs more than the shared rows save; off by default.
-bool lm_strips() {
-  static const bool on = getenv("ORIGIN_LOCALMAX_STRIPS") && atoi(getenv("ORIGIN_LOCALMAX_STRIPS")) != 0;
-  return on;
-}
-
-// the launch geometry of the sparse pass (local_max3s_kernel)
-LmGeom lm_geometry(const origin_ctx *ctx, int Nz, int Ny, int Nx) {
-  const int R = LMS_R;
-  const long threads = (long)cdiv(Ny, R) * (Nx / LMS_NC);
-  LmGeom g;
-  g.bx = (threads + 4 * 62 - 1) / (4 * 62);  // 62 producing lanes per wave
-  if (lm_strips())  // strips of four row groups x chunks of 62 columns
-    g.bx = (long)cdiv(cdiv(Ny, R), 4) * cdiv(Nx / LMS_NC, 62);
-  int nzc = (int)(((long)ctx->num_cu * 16 + g.bx - 1) / g.bx);  // ~16 blocks per CU
-  nzc = nzc < 1 ? 1 : (nzc > cdiv(Nz, 32) ? cdiv(Nz, 32) : nzc);
-  g.zp = cdiv(Nz, nzc);
-  g.nzc = cdiv(Nz, g.zp);
-  return g;
-}
-
-}  // namespace
-
 extern "C" {
 
 int origin_local_max_sparse_plan(origin_ctx *ctx, int Nz, int Ny, int Nx, long *nseg, int *seg_cap) {
@@ -734,9 +599,9 @@ int origin_local_max_sparse_plan(origin_ctx *ctx, int Nz, int Ny, int Nx, long *
   ORIGIN_CHECK_ARG(Nz > 0 && Ny > 0 && Nx > 0 && nseg && seg_cap, "bad arguments");
   *nseg = 0, *seg_cap = 0;
   if ((Nx & 3) != 0 || Nz > 65535 * 32) return ORIGIN_OK;  // no sparse form for this shape
-  const LmGeom g = lm_geometry(ctx, Nz, Ny, Nx);
+  const LmGeom g = lm_geometry(ctx, Nz, Ny, Nx, LMS_R, LMS_NC);
   *nseg = g.bx * g.nzc * 4;
-  // a wave sees zp channels of 62 lanes x 16 outputs; white noise has one 3x3x3 maximum in 27
+  // a wave sees zp channels of 62 lanes x R x NC outputs; white noise has one 3x3x3 maximum in 27
   // voxels, a smoothed cube one in ~70: room for one in 8
   const long per_wave = (long)g.zp * 62 * LMS_NC * LMS_R;
   long cap = (per_wave / 8 + 63) / 64 * 64;
@@ -754,39 +619,19 @@ int origin_local_max_sparse(origin_ctx *ctx, const float *d_correl, const float 
   ORIGIN_CHECK_ARG(Nz > 0 && Ny > 0 && (Nx & 3) == 0 && Nx > 0, "the sparse form needs Nx % 4 == 0");
   ORIGIN_CHECK_ARG(((uintptr_t)d_correl & 15) == 0 && ((uintptr_t)d_correl_min & 15) == 0 &&
                        ((uintptr_t)d_mask & 3) == 0, "cubes must be 16-byte aligned");
-  const LmGeom g = lm_geometry(ctx, Nz, Ny, Nx);
+  const LmGeom g = lm_geometry(ctx, Nz, Ny, Nx, LMS_R, LMS_NC);
   ORIGIN_CHECK_ARG(nseg == g.bx * g.nzc * 4 && seg_cap > 0,
                    "segments do not match origin_local_max_sparse_plan for this shape");
   LmSparse sp;
   sp.idx0 = d_idx_max, sp.val0 = d_val_max, sp.idx1 = d_idx_min, sp.val1 = d_val_min;
   sp.counts = d_counts, sp.seg_cap = seg_cap;
   ProfScope ps(ctx, K_LOCAL_MAX);
-  if (getenv("ORIGIN_LOCALMAX_SPARSE_V1") && LMS_R == 4 && LMS_NC == 4)   // the first form (same segments)
-    hipLaunchKernelGGL((local_max3v_kernel<2, 4, true>), dim3((unsigned)g.bx, g.nzc), dim3(256), 0,
-                       ctx->stream, d_correl, d_correl_min, d_mask, Nz, Ny, Nx, g.zp, 1.0f,
-                       (float *)nullptr, (float *)nullptr, sp);
-  else
-  {
-    // (XCD-contiguous block order: measured 3.39 ms against 3.26 with the natural order at
-    // 3681 x 600 x 600 -- the rows two neighbouring blocks share are not what the pass waits for;
-    // off unless ORIGIN_LOCALMAX_XCD=1)
-    static const int xcd_order = getenv("ORIGIN_LOCALMAX_XCD") ? atoi(getenv("ORIGIN_LOCALMAX_XCD")) : 0;
-    // ORIGIN_LOCALMAX_PREFETCH=1: the rows of the plane after next are requested a channel ahead
-    // (24 more registers: three waves per SIMD instead of four, twice the loads in flight per wave)
-    static const int prefetch = getenv("ORIGIN_LOCALMAX_PREFETCH") ? atoi(getenv("ORIGIN_LOCALMAX_PREFETCH")) : 0;
-    const dim3 grid((unsigned)(g.bx * g.nzc * 2));
-#define LM_GO(M, P, T)                                                                           \
-  hipLaunchKernelGGL((local_max3s_kernel<M, P, T>), grid, dim3(256), 0, ctx->stream, d_correl,   \
-                     d_correl_min, d_mask, Nz, Ny, Nx, g.zp, g.bx, g.nzc, xcd_order, sp)
-    if (lm_strips()) {
-      if (d_mask) LM_GO(true, false, true);
-      else LM_GO(false, false, true);
-    } else if (d_mask && prefetch) LM_GO(true, true, false);
-    else if (d_mask) LM_GO(true, false, false);
-    else if (prefetch) LM_GO(false, true, false);
-    else LM_GO(false, false, false);
-#undef LM_GO
-  }
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(g.bx * g.nzc * 2)), dim3(256), 0, ctx->stream,
+                       d_correl, d_correl_min, d_mask, Nz, Ny, Nx, g.zp, g.bx, g.nzc, sp);
+  };
+  if (d_mask) go(local_max3s_kernel<true>);
+  else go(local_max3s_kernel<false>);
   ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }

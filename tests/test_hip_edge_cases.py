@@ -199,6 +199,38 @@ def test_local_max_small_and_ragged_shapes(hip, shape, size):
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
 
 
+@pytest.mark.parametrize("shape,size", [((7, 5, 8), 3), ((40, 9, 132), 3), ((7, 5, 10), 3),
+                                        ((7, 5, 10), 5)])
+def test_local_max_one_cube_at_a_time(ctx, shape, size):
+    """origin_local_max with a NULL correl / local_max pair, then a NULL correl_min / local_min
+    pair: the four-samples-per-lane form marching one cube (rows shorter than a wave; a wave that
+    ends inside a row and a row count that is no multiple of the lane's row group), the one-sample
+    form and the generic kernel.  The cube that was asked for equals the oracle's, the buffer that
+    was not asked for keeps its sentinel."""
+    from origin_amd import _capi
+    rng = np.random.default_rng(sum(shape) + size)
+    correl = np.round(rng.standard_normal(shape) * 2).astype(np.float32).astype(float)  # ties
+    cmin = -np.abs(np.round(rng.standard_normal(shape) * 2)).astype(np.float32).astype(float)
+    mask = rng.random(shape) < 0.1
+    ref = cpu_ref.compute_local_max(correl, cmin, mask, size)
+    dc, dm = ctx.to_device(correl, np.float32), ctx.to_device(cmin, np.float32)
+    dmask = ctx.to_device(mask, np.uint8)
+    sentinel = np.full(shape, -7.5, np.float32)
+    Nz, Ny, Nx = shape
+    for keep_max in (True, False):
+        omax, omin = ctx.to_device(sentinel), ctx.to_device(sentinel)
+        if keep_max:
+            _capi.call("origin_local_max", ctx.handle, dc.p, None, dmask.p, Nz, Ny, Nx, size,
+                       omax.p, None)
+        else:
+            _capi.call("origin_local_max", ctx.handle, None, dm.p, dmask.p, Nz, Ny, Nx, size,
+                       None, omin.p)
+        ctx.sync()
+        asked, other = (omax, omin) if keep_max else (omin, omax)
+        assert np.array_equal(asked.to_host(), ref[0 if keep_max else 1])
+        assert np.array_equal(other.to_host(), sentinel)
+
+
 def test_out_of_place_pca_keeps_unassigned_spaxels(ctx):
     """cube_faint starts as a copy of cube_std (reference lib_origin.py:799): spaxels with
     areamap == 0 must come out unchanged when the device path writes into a fresh buffer."""

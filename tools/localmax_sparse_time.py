@@ -1,7 +1,5 @@
 """The sparse local-maximum pass (origin_local_max_sparse) on device cubes of the bench size: time
-per call, algorithmic bandwidth (9 B per voxel read) and the density of maxima.  The kernel's
-variants are chosen by environment variables read once per process (ORIGIN_LOCALMAX_SPARSE_V1,
-ORIGIN_LOCALMAX_XCD, ORIGIN_LOCALMAX_PREFETCH): run once per variant.
+per call, algorithmic bandwidth (9 B per voxel read) and the density of maxima.
     python tools/localmax_sparse_time.py [N] [Nz]"""
 import os, sys, time
 import numpy as np
@@ -36,8 +34,7 @@ for _ in range(reps):
 ctx.sync()
 dt = (time.perf_counter() - t) / reps
 vox = float(Nz) * N * N
-tag = " ".join(f"{k[16:]}={os.environ[k]}" for k in sorted(os.environ) if k.startswith("ORIGIN_LOCALMAX_"))
-print(f"[{tag or 'defaults'}] {1e3 * dt:.3f} ms per call, {9 * vox / dt / 1e12:.2f} TB/s of algorithmic "
+print(f"{1e3 * dt:.3f} ms per call, {9 * vox / dt / 1e12:.2f} TB/s of algorithmic "
       f"bytes (9 B/voxel); maxima {sm.nnz / vox:.4f} / minima {sn.nnz / vox:.4f} of the voxels")
 oa, ob = kernels.local_max(ctx, a, b, m, 3)
 same = np.array_equal(sm.dense().window(0, 64, 0, 64), oa.window(0, 64, 0, 64)) and \

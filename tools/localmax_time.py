@@ -1,6 +1,5 @@
 """compute_local_max on device cubes of the bench size: time per call and algorithmic bandwidth
-(17 B per voxel) of the kernel forms (ORIGIN_LOCALMAX_FORM / ORIGIN_LOCALMAX_SCALAR are read once
-per process: run once per form).      python tools/localmax_time.py [N] [Nz]"""
+(17 B per voxel).      python tools/localmax_time.py [N] [Nz]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,8 +31,7 @@ for _ in range(reps):
 ctx.sync()
 dt = (time.perf_counter() - t) / reps
 vox = float(Nz) * N * N
-print(f"form {os.environ.get('ORIGIN_LOCALMAX_FORM', '0')} scalar {os.environ.get('ORIGIN_LOCALMAX_SCALAR', '-')}: "
-      f"{1e3 * dt:.3f} ms per call, {17 * vox / dt / 1e12:.2f} TB/s of algorithmic bytes (17 B/voxel)")
+print(f"{1e3 * dt:.3f} ms per call, {17 * vox / dt / 1e12:.2f} TB/s of algorithmic bytes (17 B/voxel)")
 # spot check against NumPy on a slab
 from oracle import cpu_ref
 sl = (slice(100, 108), slice(0, 40), slice(N - 44, N))
