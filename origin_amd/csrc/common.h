@@ -42,68 +42,80 @@ struct OriginProfEvent {
   int id;
 };
 
-struct origin_ctx {
-  int device;
-  hipStream_t stream;
-  hipEvent_t ev_start[64];
-  hipEvent_t ev_stop[64];
-  bool ev_made[64];
-  // grow-only scratch for partial reductions
-  void *scratch;
-  size_t scratch_bytes;
-  int num_cu;
-  // cached DCT cosine table (dct.hip)
-  double *ctab;
-  int ctab_nz, ctab_order;
-  // per-kernel-class timing with HIP events on the stream the kernels run on
-  int prof_level;  // 0 off, 1 coarse (one scope per large kernel / per PCA run), 2 + every PCA kernel
-  std::vector<OriginProfEvent> prof_pending;
-  std::vector<hipEvent_t> prof_free;
-  double prof_ms[K_COUNT];
-  long prof_n[K_COUNT];
-  // persistent workspace of origin_pca_run (owned by pca.hip)
-  void *pca_ws;
-  void (*pca_ws_free)(void *);
-  // Auxiliary low-priority stream: HBM-bound passes nothing downstream waits for (the cont_dct
-  // cube; the final F = X - U C of areas that have finished) run here in the shadow of the greedy
-  // PCA's latency-bound kernels.  aux_join is recorded after the last piece of aux work;
-  // origin_aux_join() makes the main stream wait for it, origin_sync() waits for both streams.
-  hipStream_t aux_stream;
-  hipEvent_t aux_fork, aux_join;
-  bool aux_pending;
-  void *aux_scratch;
-  size_t aux_scratch_bytes;
-  // pinned staging of origin_d2h_f32_as_f64 / origin_h2d_f64_as_f32: two 64 MiB buffers and two
-  // events, made by the first conversion call on this context (all or nothing) and freed with it
-  float *cvt_stage[2];
-  hipEvent_t cvt_ev[2];
-  bool cvt_ready;
-  // Side stream of the row-band GLR (origin_glr_run_rows with ORIGIN_GLR_SIDE): restricted to the
-  // first num_cu - reserve compute units, so that a band started while the greedy PCA still
-  // iterates over its last areas leaves CUs to the PCA's small kernels.  side_join is recorded
-  // behind the band; origin_glr_run_finish / origin_sync wait for it.
-  hipStream_t side_stream;
-  hipEvent_t side_fork, side_join;
-  bool side_pending;
-  // greedy PCA: called once, when at most pca_tail_max areas still iterate, after the areas that
-  // have finished were written to the output (origin_pca_set_tail_hook, pca.hip)
-  void (*pca_tail_hook)(void *user, int n_active, const int *areas);
-  void *pca_tail_user;
-  int pca_tail_max;
-  // device blocks released by origin_free and kept for the next origin_malloc of their size
-  // (ctx.hip: a hipMalloc of a 5 GB cube takes ~40 ms, a hipFree synchronises the device)
-  void *alloc_cache;
+constexpr int ORIGIN_TIMER_SLOTS = 64;
+
+// a device buffer that only grows (origin_grow)
+struct GrowBuffer {
+  void *p = nullptr;
+  size_t bytes = 0;
 };
 
-// side stream plumbing (ctx.hip)
-int origin_side_begin(origin_ctx *ctx);  // side waits for the main stream's work so far
-int origin_side_end(origin_ctx *ctx);    // marks the end of the side work enqueued
-int origin_side_join(origin_ctx *ctx);   // main waits for the side work
+// A second stream beside the context's main one, made on first use.  begin: the stream waits for
+// what the main stream has been given so far; end: `join` is recorded behind the work enqueued
+// since and `pending` set; join: the main stream waits for `join` (no host sync); wait: the host
+// does.  The last two clear `pending` and do nothing where nothing is pending.
+struct ForkStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  bool pending = false;
+};
 
-// aux stream plumbing (ctx.hip)
-int origin_aux_begin(origin_ctx *ctx);                        // aux waits for the main stream's work so far
-int origin_aux_end(origin_ctx *ctx);                          // marks the end of the aux work enqueued
-int origin_aux_scratch(origin_ctx *ctx, size_t bytes, void **out);
+struct AllocCache;  // ctx.hip
+
+struct origin_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_start[ORIGIN_TIMER_SLOTS] = {};
+  hipEvent_t ev_stop[ORIGIN_TIMER_SLOTS] = {};
+  bool ev_made[ORIGIN_TIMER_SLOTS] = {};
+  GrowBuffer scratch;  // partial reductions of the main stream's kernels
+  int num_cu = 0;
+  // cached DCT cosine table (dct.hip)
+  double *ctab = nullptr;
+  int ctab_nz = 0, ctab_order = 0;
+  // per-kernel-class timing with HIP events on the stream the kernels run on
+  int prof_level = 0;  // 0 off, 1 coarse (one scope per large kernel / per PCA run), 2 + every PCA kernel
+  std::vector<OriginProfEvent> prof_pending;
+  std::vector<hipEvent_t> prof_free;
+  double prof_ms[K_COUNT] = {};
+  long prof_n[K_COUNT] = {};
+  // persistent workspace of origin_pca_run (owned by pca.hip)
+  void *pca_ws = nullptr;
+  void (*pca_ws_free)(void *) = nullptr;
+  // Auxiliary stream, of the lowest priority: an HBM-bound pass nothing downstream waits for (the
+  // cont_dct cube of origin_dct_cont_std_async) runs here in the shadow of the greedy PCA's
+  // latency-bound kernels, with a scratch of its own (the PCA uses the main one).
+  // origin_aux_join() makes the main stream wait for it, origin_sync() waits for every stream.
+  ForkStream aux;
+  GrowBuffer aux_scratch;
+  // Side stream of the row-band GLR (origin_glr_run_rows with ORIGIN_GLR_SIDE): restricted to the
+  // first num_cu - reserve compute units, so that a band started while the greedy PCA still
+  // iterates over its last areas leaves CUs to the PCA's small kernels.  Its join event is
+  // recorded behind the band; origin_glr_run_finish / origin_sync wait for it.
+  ForkStream side;
+  // pinned staging of every host copy of 32 MiB or more (origin_h2d, origin_d2h) and of the two
+  // conversions (origin_d2h_f32_as_f64, origin_h2d_f64_as_f32): two 64 MiB buffers and two events,
+  // made by the first such call on this context (all or nothing) and freed with it
+  char *stage_buf[2] = {nullptr, nullptr};
+  hipEvent_t stage_ev[2] = {nullptr, nullptr};
+  bool stage_ready = false;
+  // greedy PCA: called once, when at most pca_tail_max areas still iterate, after the areas that
+  // have finished were written to the output (origin_pca_set_tail_hook, pca.hip)
+  void (*pca_tail_hook)(void *user, int n_active, const int *areas) = nullptr;
+  void *pca_tail_user = nullptr;
+  int pca_tail_max = 0;
+  // device blocks released by origin_free and kept for the next origin_malloc of their size
+  // (ctx.hip: a hipMalloc of a 5 GB cube takes ~40 ms, a hipFree synchronises the device)
+  AllocCache *alloc_cache = nullptr;
+};
+
+// forked-stream plumbing (ctx.hip); `create` makes the stream on first use
+int origin_make_aux_stream(origin_ctx *ctx, hipStream_t *out);
+int origin_make_side_stream(origin_ctx *ctx, hipStream_t *out);
+int origin_fork_begin(origin_ctx *ctx, ForkStream &f, int (*create)(origin_ctx *, hipStream_t *));
+int origin_fork_end(ForkStream &f);
+int origin_fork_join(origin_ctx *ctx, ForkStream &f);
+int origin_fork_wait(ForkStream &f);
 
 // An event pair costs ~10 us of stream time on this hardware (barrier packets): 13 scopes in each
 // of the 56 PCA iterations add 5 ms to a 95 ms step.  Scopes therefore carry a level; bench.py
@@ -132,7 +144,11 @@ struct ProfScope {
 };
 
 void origin_set_error(const char *fmt, ...);
-int origin_scratch(origin_ctx *ctx, size_t bytes, void **out);
+// at least `bytes` of b; before a smaller buffer is freed, `sync` (the stream that used it) drains
+int origin_grow(GrowBuffer &b, size_t bytes, hipStream_t sync, void **out);
+static inline int origin_scratch(origin_ctx *ctx, size_t bytes, void **out) {
+  return origin_grow(ctx->scratch, bytes, ctx->stream, out);
+}
 
 // glr_spatial_mfma.hip: matrix-core spatial GLR stage (one field, or one weighted field of a
 // mosaic: W its weight map, accf = add to what the fields before left in out)

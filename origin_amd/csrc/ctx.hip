@@ -15,9 +15,41 @@ void origin_host_pool_run(int n, const std::function<void(int)> &task);  // thre
 
 static thread_local char g_err[1024] = "";
 
-static void alloc_cache_release(origin_ctx *ctx, bool destroy);  // (allocation cache, below)
-static void alloc_cache_make(origin_ctx *ctx);
-static size_t alloc_cache_spare(origin_ctx *ctx);
+// Blocks of at least 1 MiB that origin_free releases are kept (up to ORIGIN_ALLOC_CACHE_GB, default
+// 96, 0 = off) and handed to the next origin_malloc that asks for their size or up to an eighth
+// less.  The Step seam allocates every output of every step afresh (the reference's steps return
+// new arrays): at 3681 x 600 x 600 that was 27 allocations of up to 5.3 GB at ~40 ms each -- 1.2 s
+// of a 3.2 s pass (tools/e2e_profile.py) -- and a device-wide synchronisation per release.  Reuse
+// is ordered by the context's stream: origin_free makes it wait for the auxiliary and side streams,
+// and every kernel of the library runs on one of the three.
+struct AllocCache {
+  std::mutex mu;
+  std::unordered_map<void *, size_t> live;     // blocks handed out (>= ALLOC_MIN): their sizes
+  std::multimap<size_t, void *> spare;         // released blocks by size
+  size_t spare_bytes = 0, cap_bytes = 0;
+};
+constexpr size_t ALLOC_MIN = (size_t)1 << 20;
+
+static size_t alloc_cache_spare(AllocCache *c) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  return c->spare_bytes;
+}
+
+static void alloc_cache_release(origin_ctx *ctx, bool destroy) {
+  AllocCache *c = ctx->alloc_cache;
+  if (!c) return;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->spare.empty()) (void)hipStreamSynchronize(ctx->stream);
+    for (auto &kv : c->spare) (void)hipFree(kv.second);
+    c->spare.clear();
+    c->spare_bytes = 0;
+  }
+  if (destroy) {
+    delete c;
+    ctx->alloc_cache = nullptr;
+  }
+}
 
 // strided (nz, ny, rowbytes) box copy, device to device; 16 bytes per thread when aligned
 __global__ __launch_bounds__(256) void copy_box_kernel(char *__restrict__ dst, long dpy, long dpz,
@@ -45,111 +77,85 @@ void origin_set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
-int origin_scratch(origin_ctx *ctx, size_t bytes, void **out) {
-  if (bytes > ctx->scratch_bytes) {
-    if (ctx->scratch) {
-      ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
-      ORIGIN_HIP(hipFree(ctx->scratch));
-      ctx->scratch = nullptr;
-      ctx->scratch_bytes = 0;
+int origin_grow(GrowBuffer &b, size_t bytes, hipStream_t sync, void **out) {
+  if (bytes > b.bytes) {
+    if (b.p) {
+      if (sync) ORIGIN_HIP(hipStreamSynchronize(sync));
+      ORIGIN_HIP(hipFree(b.p));
+      b.p = nullptr;
+      b.bytes = 0;
     }
-    size_t want = bytes + bytes / 4 + (1 << 20);
-    ORIGIN_HIP(hipMalloc(&ctx->scratch, want));
-    ctx->scratch_bytes = want;
+    const size_t want = bytes + bytes / 4 + (1 << 20);
+    ORIGIN_HIP(hipMalloc(&b.p, want));
+    b.bytes = want;
   }
-  *out = ctx->scratch;
+  *out = b.p;
   return ORIGIN_OK;
 }
 
-// The side stream, made on first use: every CU but the last `reserve` (ORIGIN_GLR_SIDE_RESERVE,
-// default an eighth of the chip: 32 of 256).  Measured at 3681 x 600 x 600 with the GLR's early
-// bands beside the greedy PCA's tail (tools/tail_overlap_tune.sh, profiles/r03_tail_overlap_tune.txt):
-// step 55.8 ms with no reserve (the PCA's small kernels wait for a GLR workgroup to leave a CU: no
-// better than running the two in sequence, 55.9), 53.8 / 53.3 / 53.1 with 8 / 16 / 24 CUs,
-// 51.9 with 32, 52.4 / 52.7 / 53.0 with 40 / 64 / 96.  Work enqueued on the stream afterwards starts
-// behind everything the main stream has been given so far.
-int origin_side_begin(origin_ctx *ctx) {
-  if (!ctx->side_stream) {
-    const char *e = getenv("ORIGIN_GLR_SIDE_RESERVE");
-    const int ncu = ctx->num_cu > 0 ? std::min(ctx->num_cu, 256) : 256;
-    int reserve = e ? atoi(e) : ncu / 8;
-    reserve = std::max(0, std::min(reserve, ncu - 8));
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < ncu - reserve; ++i) mask[i >> 5] |= 1u << (i & 31);
-    if (hipExtStreamCreateWithCUMask(&ctx->side_stream, 8, mask) != hipSuccess) {
-      // (no CU masks on this runtime: a stream of the lowest priority still gives correct results,
-      // only less of an overlap -- the main stream's small kernels wait for CUs)
-      (void)hipGetLastError();
-      int lo = 0, hi = 0;
-      ORIGIN_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      ORIGIN_HIP(hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, lo));
-    }
-    ORIGIN_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-    ORIGIN_HIP(hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming));
-  }
-  ORIGIN_HIP(hipEventRecord(ctx->side_fork, ctx->stream));
-  ORIGIN_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
-  return ORIGIN_OK;
-}
-
-int origin_side_end(origin_ctx *ctx) {
-  ORIGIN_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
-  ctx->side_pending = true;
-  return ORIGIN_OK;
-}
-
-// the main stream waits for what the side stream was given
-int origin_side_join(origin_ctx *ctx) {
-  if (ctx->side_stream && ctx->side_pending) {
-    ORIGIN_HIP(hipStreamWaitEvent(ctx->stream, ctx->side_join, 0));
-    ctx->side_pending = false;
+// The side stream: every CU but the last `reserve` (ORIGIN_GLR_SIDE_RESERVE, default an eighth of
+// the chip: 32 of 256).  Measured at 3681 x 600 x 600 with the GLR's early bands beside the greedy
+// PCA's tail (tools/tail_overlap_tune.sh, profiles/r03_tail_overlap_tune.txt): step 55.8 ms with
+// no reserve (the PCA's small kernels wait for a GLR workgroup to leave a CU: no better than
+// running the two in sequence, 55.9), 53.8 / 53.3 / 53.1 with 8 / 16 / 24 CUs, 51.9 with 32,
+// 52.4 / 52.7 / 53.0 with 40 / 64 / 96.
+int origin_make_side_stream(origin_ctx *ctx, hipStream_t *out) {
+  const char *e = getenv("ORIGIN_GLR_SIDE_RESERVE");
+  const int ncu = ctx->num_cu > 0 ? std::min(ctx->num_cu, 256) : 256;
+  int reserve = e ? atoi(e) : ncu / 8;
+  reserve = std::max(0, std::min(reserve, ncu - 8));
+  uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < ncu - reserve; ++i) mask[i >> 5] |= 1u << (i & 31);
+  if (hipExtStreamCreateWithCUMask(out, 8, mask) != hipSuccess) {
+    // (no CU masks on this runtime: a stream of the lowest priority still gives correct results,
+    // only less of an overlap -- the main stream's small kernels wait for CUs)
+    (void)hipGetLastError();
+    return origin_make_aux_stream(ctx, out);
   }
   return ORIGIN_OK;
 }
 
-// The aux stream is created on first use, with the lowest priority the device offers: its
-// thousands of HBM-bound workgroups must not sit in front of the one-block kernels of the PCA.
-int origin_aux_begin(origin_ctx *ctx) {
-  if (!ctx->aux_stream) {
-    // ORIGIN_AUX_CUS=n: restrict the stream to n CUs (hipExtStreamCreateWithCUMask), leaving the
-    // rest of the chip to the main stream's small kernels; default: lowest priority, all CUs
-    const char *cus = getenv("ORIGIN_AUX_CUS");
-    if (cus && atoi(cus) > 0) {
-      const int n = std::min(atoi(cus), ctx->num_cu > 0 ? ctx->num_cu : 256);
-      uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int i = 0; i < n; ++i) mask[i >> 5] |= 1u << (i & 31);
-      ORIGIN_HIP(hipExtStreamCreateWithCUMask(&ctx->aux_stream, 8, mask));
-    } else {
-      int lo = 0, hi = 0;
-      ORIGIN_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));  // lo = least urgent
-      ORIGIN_HIP(hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, lo));
-    }
-    ORIGIN_HIP(hipEventCreateWithFlags(&ctx->aux_fork, hipEventDisableTiming));
-    ORIGIN_HIP(hipEventCreateWithFlags(&ctx->aux_join, hipEventDisableTiming));
-  }
-  ORIGIN_HIP(hipEventRecord(ctx->aux_fork, ctx->stream));
-  ORIGIN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
+// The aux stream has the lowest priority the device offers: its thousands of HBM-bound workgroups
+// must not sit in front of the one-block kernels of the PCA.
+int origin_make_aux_stream(origin_ctx *, hipStream_t *out) {
+  int lo = 0, hi = 0;
+  ORIGIN_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));  // lo = least urgent
+  ORIGIN_HIP(hipStreamCreateWithPriority(out, hipStreamNonBlocking, lo));
   return ORIGIN_OK;
 }
 
-int origin_aux_end(origin_ctx *ctx) {
-  ORIGIN_HIP(hipEventRecord(ctx->aux_join, ctx->aux_stream));
-  ctx->aux_pending = true;
+// Work enqueued on the stream afterwards starts behind everything the main stream has been given
+// so far.
+int origin_fork_begin(origin_ctx *ctx, ForkStream &f, int (*create)(origin_ctx *, hipStream_t *)) {
+  if (!f.stream) {
+    if (int rc = create(ctx, &f.stream)) return rc;
+    ORIGIN_HIP(hipEventCreateWithFlags(&f.fork, hipEventDisableTiming));
+    ORIGIN_HIP(hipEventCreateWithFlags(&f.join, hipEventDisableTiming));
+  }
+  ORIGIN_HIP(hipEventRecord(f.fork, ctx->stream));
+  ORIGIN_HIP(hipStreamWaitEvent(f.stream, f.fork, 0));
   return ORIGIN_OK;
 }
 
-int origin_aux_scratch(origin_ctx *ctx, size_t bytes, void **out) {
-  if (bytes > ctx->aux_scratch_bytes) {
-    if (ctx->aux_scratch) {
-      if (ctx->aux_stream) ORIGIN_HIP(hipStreamSynchronize(ctx->aux_stream));
-      ORIGIN_HIP(hipFree(ctx->aux_scratch));
-      ctx->aux_scratch = nullptr;
-      ctx->aux_scratch_bytes = 0;
-    }
-    ORIGIN_HIP(hipMalloc(&ctx->aux_scratch, bytes + bytes / 4 + (1 << 20)));
-    ctx->aux_scratch_bytes = bytes + bytes / 4 + (1 << 20);
+int origin_fork_end(ForkStream &f) {
+  ORIGIN_HIP(hipEventRecord(f.join, f.stream));
+  f.pending = true;
+  return ORIGIN_OK;
+}
+
+int origin_fork_join(origin_ctx *ctx, ForkStream &f) {
+  if (f.stream && f.pending) {
+    ORIGIN_HIP(hipStreamWaitEvent(ctx->stream, f.join, 0));
+    f.pending = false;
   }
-  *out = ctx->aux_scratch;
+  return ORIGIN_OK;
+}
+
+int origin_fork_wait(ForkStream &f) {
+  if (f.stream && f.pending) {
+    ORIGIN_HIP(hipStreamSynchronize(f.stream));
+    f.pending = false;
+  }
   return ORIGIN_OK;
 }
 
@@ -259,45 +265,7 @@ int origin_ctx_create(int device, origin_ctx **out) {
   ORIGIN_HIP(hipSetDevice(device));
   origin_ctx *ctx = new origin_ctx();
   ctx->device = device;
-  ctx->stream = nullptr;
-  memset(ctx->ev_made, 0, sizeof(ctx->ev_made));
-  ctx->scratch = nullptr;
-  ctx->scratch_bytes = 0;
-  ctx->num_cu = 0;
-  ctx->ctab = nullptr;
-  ctx->ctab_nz = ctx->ctab_order = 0;
-  ctx->prof_level = false;
-  ctx->pca_ws = nullptr;
-  ctx->pca_ws_free = nullptr;
-  ctx->aux_stream = nullptr;
-  ctx->aux_fork = ctx->aux_join = nullptr;
-  ctx->aux_pending = false;
-  ctx->aux_scratch = nullptr;
-  ctx->aux_scratch_bytes = 0;
-  ctx->cvt_stage[0] = ctx->cvt_stage[1] = nullptr;
-  ctx->cvt_ready = false;
-  memset(ctx->prof_ms, 0, sizeof(ctx->prof_ms));
-  memset(ctx->prof_n, 0, sizeof(ctx->prof_n));
-  // ORIGIN_CTX_PRIORITY=high|low: queue priority of this context's main stream (measurements of
-  // concurrent contexts: a latency-bound chain beside a chip-filling pass, tools/pca_glr_overlap.py)
-  hipError_t e;
-  const char *prio = getenv("ORIGIN_CTX_PRIORITY");
-  // ORIGIN_CTX_CUS=n: this context's main stream may use the first n compute units only
-  // (hipExtStreamCreateWithCUMask) -- leaves the others to a concurrent context's small kernels
-  const char *cus = getenv("ORIGIN_CTX_CUS");
-  int masked_cus = 0;
-  if (cus && atoi(cus) > 0 && atoi(cus) < 256) {
-    masked_cus = atoi(cus);
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < masked_cus; ++i) mask[i >> 5] |= 1u << (i & 31);
-    e = hipExtStreamCreateWithCUMask(&ctx->stream, 8, mask);
-  } else if (prio && (!strcmp(prio, "high") || !strcmp(prio, "low"))) {
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = least urgent, hi = most urgent
-    e = hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio[0] == 'h' ? hi : lo);
-  } else {
-    e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  }
+  hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete ctx;
     origin_set_error("hipStreamCreate: %s", hipGetErrorString(e));
@@ -306,8 +274,9 @@ int origin_ctx_create(int device, origin_ctx **out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->num_cu = prop.multiProcessorCount;
   if (ctx->num_cu <= 0) ctx->num_cu = 256;
-  if (masked_cus > 0 && masked_cus < ctx->num_cu) ctx->num_cu = masked_cus;  // (grids are sized by it)
-  alloc_cache_make(ctx);
+  ctx->alloc_cache = new AllocCache();
+  const char *gb = getenv("ORIGIN_ALLOC_CACHE_GB");
+  ctx->alloc_cache->cap_bytes = (size_t)((gb ? atof(gb) : 96.0) * 1e9);
   *out = ctx;
   return ORIGIN_OK;
 }
@@ -316,32 +285,27 @@ int origin_ctx_destroy(origin_ctx *ctx) {
   if (!ctx) return ORIGIN_OK;
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
-  for (int i = 0; i < 64; ++i)
+  for (int i = 0; i < ORIGIN_TIMER_SLOTS; ++i)
     if (ctx->ev_made[i]) {
       hipEventDestroy(ctx->ev_start[i]);
       hipEventDestroy(ctx->ev_stop[i]);
     }
-  if (ctx->aux_stream) {
-    hipStreamSynchronize(ctx->aux_stream);
-    hipStreamDestroy(ctx->aux_stream);
-    hipEventDestroy(ctx->aux_fork);
-    hipEventDestroy(ctx->aux_join);
-  }
-  if (ctx->side_stream) {
-    hipStreamSynchronize(ctx->side_stream);
-    hipStreamDestroy(ctx->side_stream);
-    hipEventDestroy(ctx->side_fork);
-    hipEventDestroy(ctx->side_join);
-  }
-  if (ctx->cvt_ready) {
+  for (ForkStream *f : {&ctx->aux, &ctx->side})
+    if (f->stream) {
+      hipStreamSynchronize(f->stream);
+      hipStreamDestroy(f->stream);
+      hipEventDestroy(f->fork);
+      hipEventDestroy(f->join);
+    }
+  if (ctx->stage_ready) {
     for (int b = 0; b < 2; ++b) {
-      hipHostFree(ctx->cvt_stage[b]);
-      hipEventDestroy(ctx->cvt_ev[b]);
+      hipHostFree(ctx->stage_buf[b]);
+      hipEventDestroy(ctx->stage_ev[b]);
     }
   }
   alloc_cache_release(ctx, true);
-  if (ctx->aux_scratch) hipFree(ctx->aux_scratch);
-  if (ctx->scratch) hipFree(ctx->scratch);
+  if (ctx->aux_scratch.p) hipFree(ctx->aux_scratch.p);
+  if (ctx->scratch.p) hipFree(ctx->scratch.p);
   if (ctx->ctab) hipFree(ctx->ctab);
   if (ctx->pca_ws && ctx->pca_ws_free) ctx->pca_ws_free(ctx->pca_ws);
   prof_drain(ctx);
@@ -353,25 +317,14 @@ int origin_ctx_destroy(origin_ctx *ctx) {
 
 int origin_sync(origin_ctx *ctx) {
   ORIGIN_USE(ctx);
-  if (ctx->side_stream && ctx->side_pending) {
-    ORIGIN_HIP(hipStreamSynchronize(ctx->side_stream));
-    ctx->side_pending = false;
-  }
+  if (int rc = origin_fork_wait(ctx->side)) return rc;
   ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->aux_stream && ctx->aux_pending) {
-    ORIGIN_HIP(hipStreamSynchronize(ctx->aux_stream));
-    ctx->aux_pending = false;
-  }
-  return ORIGIN_OK;
+  return origin_fork_wait(ctx->aux);
 }
 
 int origin_aux_join(origin_ctx *ctx) {
   ORIGIN_USE(ctx);
-  if (ctx->aux_stream && ctx->aux_pending) {
-    ORIGIN_HIP(hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0));
-    ctx->aux_pending = false;
-  }
-  return ORIGIN_OK;
+  return origin_fork_join(ctx, ctx->aux);
 }
 
 int origin_device_name(origin_ctx *ctx, char *buf, int buflen) {
@@ -387,7 +340,7 @@ int origin_mem_info(origin_ctx *ctx, size_t *free_bytes, size_t *total_bytes) {
   ORIGIN_USE(ctx);
   size_t f = 0, t = 0;
   ORIGIN_HIP(hipMemGetInfo(&f, &t));
-  if (free_bytes) *free_bytes = f + alloc_cache_spare(ctx);  // (spare blocks go back when memory runs out)
+  if (free_bytes) *free_bytes = f + alloc_cache_spare(ctx->alloc_cache);  // (spare blocks go back when memory runs out)
   if (total_bytes) *total_bytes = t;
   return ORIGIN_OK;
 }
@@ -399,57 +352,12 @@ int origin_stream(origin_ctx *ctx, void **stream) {
   return ORIGIN_OK;
 }
 
-// Blocks of at least 1 MiB that origin_free releases are kept (up to ORIGIN_ALLOC_CACHE_GB, default
-// 96, 0 = off) and handed to the next origin_malloc that asks for their size or up to an eighth
-// less.  The Step seam allocates every output of every step afresh (the reference's steps return
-// new arrays): at 3681 x 600 x 600 that was 27 allocations of up to 5.3 GB at ~40 ms each -- 1.2 s
-// of a 3.2 s pass (tools/e2e_profile.py) -- and a device-wide synchronisation per release.  Reuse
-// is ordered by the context's stream: origin_free makes it wait for the auxiliary and side streams,
-// and every kernel of the library runs on one of the three.
-struct AllocCache {
-  std::mutex mu;
-  std::unordered_map<void *, size_t> live;     // blocks handed out (>= ALLOC_MIN): their sizes
-  std::multimap<size_t, void *> spare;         // released blocks by size
-  size_t spare_bytes = 0, cap_bytes = 0;
-};
-constexpr size_t ALLOC_MIN = (size_t)1 << 20;
-
-static void alloc_cache_make(origin_ctx *ctx) {  // (origin_ctx_create)
-  auto *c = new AllocCache();
-  const char *e = getenv("ORIGIN_ALLOC_CACHE_GB");
-  c->cap_bytes = (size_t)((e ? atof(e) : 96.0) * 1e9);
-  ctx->alloc_cache = c;
-}
-static AllocCache *alloc_cache(origin_ctx *ctx) { return (AllocCache *)ctx->alloc_cache; }
-static size_t alloc_cache_spare(origin_ctx *ctx) {
-  auto *c = alloc_cache(ctx);
-  if (!c) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  return c->spare_bytes;
-}
-
-static void alloc_cache_release(origin_ctx *ctx, bool destroy) {
-  auto *c = (AllocCache *)ctx->alloc_cache;
-  if (!c) return;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->spare.empty()) (void)hipStreamSynchronize(ctx->stream);
-    for (auto &kv : c->spare) (void)hipFree(kv.second);
-    c->spare.clear();
-    c->spare_bytes = 0;
-  }
-  if (destroy) {
-    delete c;
-    ctx->alloc_cache = nullptr;
-  }
-}
-
 int origin_malloc(origin_ctx *ctx, size_t bytes, void **d_ptr) {
   ORIGIN_USE(ctx);
   ORIGIN_CHECK_ARG(d_ptr, "d_ptr is null");
   *d_ptr = nullptr;
   if (bytes == 0) bytes = 16;
-  AllocCache *c = alloc_cache(ctx);
+  AllocCache *c = ctx->alloc_cache;
   if (bytes >= ALLOC_MIN && c->cap_bytes > 0) {
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->spare.lower_bound(bytes);
@@ -462,7 +370,7 @@ int origin_malloc(origin_ctx *ctx, size_t bytes, void **d_ptr) {
     }
   }
   hipError_t e = hipMalloc(d_ptr, bytes);
-  if (e == hipErrorOutOfMemory && c->spare_bytes > 0) {  // give the spare blocks back and try again
+  if (e == hipErrorOutOfMemory && alloc_cache_spare(c) > 0) {  // give the spare blocks back and try again
     (void)hipGetLastError();
     alloc_cache_release(ctx, false);
     e = hipMalloc(d_ptr, bytes);
@@ -481,7 +389,7 @@ int origin_malloc(origin_ctx *ctx, size_t bytes, void **d_ptr) {
 int origin_free(origin_ctx *ctx, void *d_ptr) {
   ORIGIN_USE(ctx);
   if (!d_ptr) return ORIGIN_OK;
-  AllocCache *c = alloc_cache(ctx);
+  AllocCache *c = ctx->alloc_cache;
   {
     std::unique_lock<std::mutex> lk(c->mu);
     auto it = c->live.find(d_ptr);
@@ -491,14 +399,8 @@ int origin_free(origin_ctx *ctx, void *d_ptr) {
       if (c->spare_bytes + sz <= c->cap_bytes) {
         // whoever gets the block next uses it behind everything enqueued so far, on any stream
         lk.unlock();
-        if (ctx->aux_stream && ctx->aux_pending) {
-          ORIGIN_HIP(hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0));
-          ctx->aux_pending = false;
-        }
-        if (ctx->side_stream && ctx->side_pending) {
-          int rj = origin_side_join(ctx);
-          if (rj) return rj;
-        }
+        if (int rc = origin_fork_join(ctx, ctx->aux)) return rc;
+        if (int rc = origin_fork_join(ctx, ctx->side)) return rc;
         lk.lock();
         c->spare.emplace(sz, d_ptr);
         c->spare_bytes += sz;
@@ -517,55 +419,106 @@ int origin_memset(origin_ctx *ctx, void *d_ptr, int byte, size_t bytes) {
   return ORIGIN_OK;
 }
 
-static int cvt_staging(origin_ctx *ctx);
-constexpr size_t STAGED_MIN = (size_t)32 << 20;   // copies of at least this go through pinned staging
-constexpr size_t STAGED_CH = (size_t)64 << 20;    // bytes per staging buffer (= CVT_CH floats)
+constexpr size_t STAGED_MIN = (size_t)32 << 20;   // plain copies of at least this go through pinned staging
+constexpr size_t STAGED_CH = (size_t)64 << 20;    // bytes per staging buffer
+constexpr size_t STAGED_PIECE = (size_t)1 << 20;  // staging bytes per task of the host pool
 
-// Large pageable copies, both ways, in 64 MiB chunks through the context's two pinned staging
-// buffers, with the host side of every chunk -- a memcpy between the caller's pages and the
-// staging buffer -- spread over the host worker pool while the other buffer is on the bus.  A
-// pageable hipMemcpy does that memcpy on one runtime thread: 21-30 GB/s, and 22 GB/s into a fresh
-// destination whose pages fault one by one (tools/pagefault_probe.py); the float64 hand-over, which
-// works this way, reaches 45 GB/s into fresh pages.
-static int staged_h2d(origin_ctx *ctx, char *d_dst, const char *h_src, size_t bytes) {
-  int rcs = cvt_staging(ctx);
-  if (rcs) return rcs;
-  char *const stage[2] = {(char *)ctx->cvt_stage[0], (char *)ctx->cvt_stage[1]};
-  hipEvent_t *ev = ctx->cvt_ev;
-  const size_t nch = (bytes + STAGED_CH - 1) / STAGED_CH;
+// The staging buffers: owned by the context (its device, its stream), marked ready only when both
+// buffers and both events exist; a partial failure is rolled back.
+static int stage_create(origin_ctx *ctx) {
+  if (ctx->stage_ready) return ORIGIN_OK;
+  char *st[2] = {nullptr, nullptr};
+  hipEvent_t ev[2];
+  int nev = 0;
+  hipError_t e = hipSuccess;
+  for (int b = 0; b < 2 && e == hipSuccess; ++b)
+    e = hipHostMalloc((void **)&st[b], STAGED_CH, hipHostMallocDefault);
+  for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+    e = hipEventCreateWithFlags(&ev[b], hipEventDisableTiming);
+    if (e == hipSuccess) ++nev;
+  }
+  for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipEventRecord(ev[b], ctx->stream);
+  if (e != hipSuccess) {
+    for (int b = 0; b < nev; ++b) (void)hipEventDestroy(ev[b]);
+    for (int b = 0; b < 2; ++b)
+      if (st[b]) (void)hipHostFree(st[b]);
+    origin_set_error("conversion staging: %s", hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? ORIGIN_E_NOMEM : ORIGIN_E_HIP;
+  }
+  for (int b = 0; b < 2; ++b) ctx->stage_buf[b] = st[b], ctx->stage_ev[b] = ev[b];
+  ctx->stage_ready = true;
+  return ORIGIN_OK;
+}
+
+// What the host pool does to a piece of n elements between the caller's pages and a staging buffer.
+typedef void (*StagePiece)(void *__restrict__ dst, const void *__restrict__ src, size_t n);
+static void piece_copy(void *__restrict__ dst, const void *__restrict__ src, size_t n) {
+  memcpy(dst, src, n);
+}
+static void piece_widen(void *__restrict__ dst, const void *__restrict__ src, size_t n) {
+  for (size_t i = 0; i < n; ++i) ((double *)dst)[i] = (double)((const float *)src)[i];
+}
+static void piece_narrow(void *__restrict__ dst, const void *__restrict__ src, size_t n) {
+  for (size_t i = 0; i < n; ++i) ((float *)dst)[i] = (float)((const double *)src)[i];
+}
+
+// the m elements of a chunk, spread over the host pool in pieces of `per` elements
+static void stage_pieces(StagePiece piece, char *dst, size_t dst_el, const char *src, size_t src_el,
+                         size_t m, size_t per) {
+  origin_host_pool_run((int)((m + per - 1) / per), [&](int p) {
+    const size_t a = (size_t)p * per, b = std::min(m, a + per);
+    piece(dst + a * dst_el, src + a * src_el, b - a);
+  });
+}
+
+// Large copies between pageable host memory and the device, in 64 MiB chunks through the context's
+// two pinned staging buffers, with the host side of every chunk -- `piece` between the caller's
+// pages and the staging buffer, over elements of host_el bytes there and dev_el bytes on the
+// device -- spread over the host worker pool while the other buffer is on the bus.  A pageable
+// hipMemcpy does its memcpy on one runtime thread: 21-30 GB/s, and 22 GB/s into a fresh
+// destination whose pages fault one by one (tools/pagefault_probe.py); this reaches 45 GB/s into
+// fresh pages.  The conversions replace a single-threaded astype on top of that.
+static int staged_h2d(origin_ctx *ctx, char *d_dst, const char *h_src, size_t n, size_t dev_el,
+                      size_t host_el, StagePiece piece) {
+  char *const *stage = ctx->stage_buf;
+  hipEvent_t *ev = ctx->stage_ev;
+  const size_t CH = STAGED_CH / dev_el;
+  const size_t nch = (n + CH - 1) / CH;
   for (size_t c = 0; c < nch; ++c) {
-    const size_t o = c * STAGED_CH, m = std::min(STAGED_CH, bytes - o);
-    char *dst = stage[c & 1];
+    const size_t o = c * CH, m = std::min(CH, n - o);
     ORIGIN_HIP(hipEventSynchronize(ev[c & 1]));  // the copy that last read this buffer is done
-    constexpr size_t PIECE = (size_t)1 << 20;
-    const int np = (int)((m + PIECE - 1) / PIECE);
-    origin_host_pool_run(np, [&](int p) {
-      const size_t a = (size_t)p * PIECE, b = std::min(m, a + PIECE);
-      memcpy(dst + a, h_src + o + a, b - a);
-    });
-    ORIGIN_HIP(hipMemcpyAsync(d_dst + o, dst, m, hipMemcpyHostToDevice, ctx->stream));
+    stage_pieces(piece, stage[c & 1], dev_el, h_src + o * host_el, host_el, m, STAGED_PIECE / dev_el);
+    ORIGIN_HIP(hipMemcpyAsync(d_dst + o * dev_el, stage[c & 1], m * dev_el, hipMemcpyHostToDevice,
+                              ctx->stream));
     ORIGIN_HIP(hipEventRecord(ev[c & 1], ctx->stream));
   }
   ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
   return ORIGIN_OK;
 }
 
-int origin_h2d(origin_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
-  ORIGIN_USE(ctx);
-  if (bytes == 0) return ORIGIN_OK;
-  if (bytes >= STAGED_MIN) return staged_h2d(ctx, (char *)d_dst, (const char *)h_src, bytes);
-  ORIGIN_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
-  return ORIGIN_OK;
-}
-
-// Reads of device arrays by the host wait for pending work of the auxiliary stream too (cont_dct /
-// ima_dct of origin_dct_cont_std_async): a caller that forgot origin_aux_join would otherwise get
-// a half-written array without any error.
-static int aux_before_read(origin_ctx *ctx) {
-  if (ctx->aux_stream && ctx->aux_pending) {
-    ORIGIN_HIP(hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0));
-    ctx->aux_pending = false;
+// (while chunk c + 1 is in flight the host pool works on chunk c)
+static int staged_d2h(origin_ctx *ctx, char *h_dst, const char *d_src, size_t n, size_t dev_el,
+                      size_t host_el, StagePiece piece) {
+  char *const *stage = ctx->stage_buf;
+  hipEvent_t *ev = ctx->stage_ev;
+  const size_t CH = STAGED_CH / dev_el;
+  const size_t nch = (n + CH - 1) / CH;
+  ORIGIN_HIP(hipEventSynchronize(ev[0]));  // (an upload may still be reading the buffers)
+  ORIGIN_HIP(hipEventSynchronize(ev[1]));
+  auto issue = [&](size_t c) -> int {
+    const size_t o = c * CH, m = std::min(CH, n - o);
+    ORIGIN_HIP(hipMemcpyAsync(stage[c & 1], d_src + o * dev_el, m * dev_el, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    ORIGIN_HIP(hipEventRecord(ev[c & 1], ctx->stream));
+    return ORIGIN_OK;
+  };
+  int rc = issue(0);
+  if (rc) return rc;
+  for (size_t c = 0; c < nch; ++c) {
+    ORIGIN_HIP(hipEventSynchronize(ev[c & 1]));
+    if (c + 1 < nch && (rc = issue(c + 1))) return rc;
+    const size_t o = c * CH, m = std::min(CH, n - o);
+    stage_pieces(piece, h_dst + o * host_el, host_el, stage[c & 1], dev_el, m, STAGED_PIECE / dev_el);
   }
   return ORIGIN_OK;
 }
@@ -581,148 +534,56 @@ static void hint_huge_pages(void *dst, size_t bytes) {
   if (b > a) (void)madvise((void *)a, (size_t)(b - a), MADV_HUGEPAGE);
 }
 
+int origin_h2d(origin_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
+  ORIGIN_USE(ctx);
+  if (bytes == 0) return ORIGIN_OK;
+  if (bytes >= STAGED_MIN) {
+    if (int rc = stage_create(ctx)) return rc;
+    return staged_h2d(ctx, (char *)d_dst, (const char *)h_src, bytes, 1, 1, piece_copy);
+  }
+  ORIGIN_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
+  return ORIGIN_OK;
+}
+
+// Reads of device arrays by the host first make the main stream wait for pending work of the
+// auxiliary stream (cont_dct / ima_dct of origin_dct_cont_std_async: origin_fork_join on ctx->aux):
+// a caller that forgot origin_aux_join would otherwise get a half-written array without any error.
 int origin_d2h(origin_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
   ORIGIN_USE(ctx);
   if (bytes == 0) return ORIGIN_OK;
-  { int rca = aux_before_read(ctx); if (rca) return rca; }
+  if (int rc = origin_fork_join(ctx, ctx->aux)) return rc;
   hint_huge_pages(h_dst, bytes);
   if (bytes >= STAGED_MIN) {
-    int rcs = cvt_staging(ctx);
-    if (rcs) return rcs;
-    char *const stage[2] = {(char *)ctx->cvt_stage[0], (char *)ctx->cvt_stage[1]};
-    hipEvent_t *ev = ctx->cvt_ev;
-    ORIGIN_HIP(hipEventSynchronize(ev[0]));  // (an upload may still be reading the buffers)
-    ORIGIN_HIP(hipEventSynchronize(ev[1]));
-    const size_t nch = (bytes + STAGED_CH - 1) / STAGED_CH;
-    auto issue = [&](size_t c) -> int {
-      const size_t o = c * STAGED_CH, m = std::min(STAGED_CH, bytes - o);
-      ORIGIN_HIP(hipMemcpyAsync(stage[c & 1], (const char *)d_src + o, m, hipMemcpyDeviceToHost,
-                                ctx->stream));
-      ORIGIN_HIP(hipEventRecord(ev[c & 1], ctx->stream));
-      return ORIGIN_OK;
-    };
-    int rc = issue(0);
-    if (rc) return rc;
-    for (size_t c = 0; c < nch; ++c) {
-      ORIGIN_HIP(hipEventSynchronize(ev[c & 1]));
-      if (c + 1 < nch && (rc = issue(c + 1))) return rc;
-      const size_t o = c * STAGED_CH, m = std::min(STAGED_CH, bytes - o);
-      const char *src = stage[c & 1];
-      char *dst = (char *)h_dst + o;
-      constexpr size_t PIECE = (size_t)1 << 20;
-      const int np = (int)((m + PIECE - 1) / PIECE);
-      origin_host_pool_run(np, [&](int p) {
-        const size_t a = (size_t)p * PIECE, b = std::min(m, a + PIECE);
-        memcpy(dst + a, src + a, b - a);
-      });
-    }
-    return ORIGIN_OK;
+    if (int rc = stage_create(ctx)) return rc;
+    return staged_d2h(ctx, (char *)h_dst, (const char *)d_src, bytes, 1, 1, piece_copy);
   }
   ORIGIN_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
   return ORIGIN_OK;
 }
 
-// Staging of the two conversions below: owned by the context (its device, its stream), marked
-// ready only when both buffers and both events exist; a partial failure is rolled back.
-constexpr size_t CVT_CH = (size_t)16 << 20;  // elements per chunk: 64 MiB of float32
-static int cvt_staging(origin_ctx *ctx) {
-  if (ctx->cvt_ready) return ORIGIN_OK;
-  float *st[2] = {nullptr, nullptr};
-  hipEvent_t ev[2];
-  int nev = 0;
-  hipError_t e = hipSuccess;
-  for (int b = 0; b < 2 && e == hipSuccess; ++b)
-    e = hipHostMalloc((void **)&st[b], CVT_CH * sizeof(float), hipHostMallocDefault);
-  for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-    e = hipEventCreateWithFlags(&ev[b], hipEventDisableTiming);
-    if (e == hipSuccess) ++nev;
-  }
-  for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipEventRecord(ev[b], ctx->stream);
-  if (e != hipSuccess) {
-    for (int b = 0; b < nev; ++b) (void)hipEventDestroy(ev[b]);
-    for (int b = 0; b < 2; ++b)
-      if (st[b]) (void)hipHostFree(st[b]);
-    origin_set_error("conversion staging: %s", hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? ORIGIN_E_NOMEM : ORIGIN_E_HIP;
-  }
-  for (int b = 0; b < 2; ++b) ctx->cvt_stage[b] = st[b], ctx->cvt_ev[b] = ev[b];
-  ctx->cvt_ready = true;
-  return ORIGIN_OK;
-}
-
 // Device float32 -> host float64 (the reference's arrays are float64: every cube that leaves
-// through the function seam or a LazyCube is widened).  Chunks of the device array land in two
-// pinned staging buffers by turns; while chunk i + 1 is in flight the host worker pool widens chunk
-// i into the destination -- instead of a pageable copy followed by a single-threaded astype.
+// through the function seam or a LazyCube is widened)
 int origin_d2h_f32_as_f64(origin_ctx *ctx, double *h_dst, const float *d_src, size_t n) {
   ORIGIN_USE(ctx);
   if (n == 0) return ORIGIN_OK;
   ORIGIN_CHECK_ARG(h_dst && d_src, "null pointer");
-  constexpr size_t CH = CVT_CH;
-  int rcs = cvt_staging(ctx);
-  if (rcs) return rcs;
-  if ((rcs = aux_before_read(ctx))) return rcs;
-  float *const *stage = ctx->cvt_stage;
-  hipEvent_t *ev = ctx->cvt_ev;
-  // (a narrowing upload may still be reading the buffers)
-  ORIGIN_HIP(hipEventSynchronize(ev[0]));
-  ORIGIN_HIP(hipEventSynchronize(ev[1]));
-  const size_t nch = (n + CH - 1) / CH;
+  if (int rc = stage_create(ctx)) return rc;
+  if (int rc = origin_fork_join(ctx, ctx->aux)) return rc;
   hint_huge_pages(h_dst, n * sizeof(double));
-  auto issue = [&](size_t c) -> int {
-    const size_t o = c * CH, m = std::min(CH, n - o);
-    ORIGIN_HIP(hipMemcpyAsync(stage[c & 1], d_src + o, m * sizeof(float), hipMemcpyDeviceToHost,
-                              ctx->stream));
-    ORIGIN_HIP(hipEventRecord(ev[c & 1], ctx->stream));
-    return ORIGIN_OK;
-  };
-  int rc = issue(0);
-  if (rc) return rc;
-  for (size_t c = 0; c < nch; ++c) {
-    ORIGIN_HIP(hipEventSynchronize(ev[c & 1]));
-    if (c + 1 < nch && (rc = issue(c + 1))) return rc;
-    const size_t o = c * CH, m = std::min(CH, n - o);
-    const float *src = stage[c & 1];
-    double *dst = h_dst + o;
-    constexpr size_t PIECE = (size_t)1 << 18;  // 1 MiB of float32 per task
-    const int np = (int)((m + PIECE - 1) / PIECE);
-    origin_host_pool_run(np, [&](int p) {
-      const size_t a = (size_t)p * PIECE, b = std::min(m, a + PIECE);
-      for (size_t i = a; i < b; ++i) dst[i] = (double)src[i];
-    });
-  }
-  return ORIGIN_OK;
+  return staged_d2h(ctx, (char *)h_dst, (const char *)d_src, n, sizeof(float), sizeof(double),
+                    piece_widen);
 }
 
-// Host float64 -> device float32 (the reference hands float64 cubes to the function seam): the
-// host pool narrows chunk i + 1 into a pinned staging buffer while chunk i is on its way.
+// Host float64 -> device float32 (the reference hands float64 cubes to the function seam)
 int origin_h2d_f64_as_f32(origin_ctx *ctx, float *d_dst, const double *h_src, size_t n) {
   ORIGIN_USE(ctx);
   if (n == 0) return ORIGIN_OK;
   ORIGIN_CHECK_ARG(d_dst && h_src, "null pointer");
-  constexpr size_t CH = CVT_CH;
-  int rcs = cvt_staging(ctx);
-  if (rcs) return rcs;
-  float *const *stage = ctx->cvt_stage;
-  hipEvent_t *ev = ctx->cvt_ev;
-  const size_t nch = (n + CH - 1) / CH;
-  for (size_t c = 0; c < nch; ++c) {
-    const size_t o = c * CH, m = std::min(CH, n - o);
-    float *dst = stage[c & 1];
-    const double *src = h_src + o;
-    ORIGIN_HIP(hipEventSynchronize(ev[c & 1]));  // the copy that last read this buffer is done
-    constexpr size_t PIECE = (size_t)1 << 18;
-    const int np = (int)((m + PIECE - 1) / PIECE);
-    origin_host_pool_run(np, [&](int p) {
-      const size_t a = (size_t)p * PIECE, b = std::min(m, a + PIECE);
-      for (size_t i = a; i < b; ++i) dst[i] = (float)src[i];
-    });
-    ORIGIN_HIP(hipMemcpyAsync(d_dst + o, dst, m * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    ORIGIN_HIP(hipEventRecord(ev[c & 1], ctx->stream));
-  }
-  ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
-  return ORIGIN_OK;
+  if (int rc = stage_create(ctx)) return rc;
+  return staged_h2d(ctx, (char *)d_dst, (const char *)h_src, n, sizeof(float), sizeof(double),
+                    piece_narrow);
 }
 
 int origin_d2d(origin_ctx *ctx, void *d_dst, const void *d_src, size_t bytes) {
@@ -745,7 +606,7 @@ int origin_copy_box(origin_ctx *ctx, int kind, void *dst, long dst_pitch_y, long
                    "plane pitch smaller than a row");
   if (nz == 0 || ny == 0 || nx == 0) return ORIGIN_OK;
   if (kind == 1) {
-    int rca = aux_before_read(ctx);
+    int rca = origin_fork_join(ctx, ctx->aux);
     if (rca) return rca;
   }
   hipMemcpyKind k = kind == 0   ? hipMemcpyHostToDevice
@@ -779,7 +640,7 @@ int origin_copy_box(origin_ctx *ctx, int kind, void *dst, long dst_pitch_y, long
 
 int origin_timer_start(origin_ctx *ctx, int slot) {
   ORIGIN_USE(ctx);
-  ORIGIN_CHECK_ARG(slot >= 0 && slot < 64, "timer slot out of range");
+  ORIGIN_CHECK_ARG(slot >= 0 && slot < ORIGIN_TIMER_SLOTS, "timer slot out of range");
   if (!ctx->ev_made[slot]) {
     ORIGIN_HIP(hipEventCreate(&ctx->ev_start[slot]));
     ORIGIN_HIP(hipEventCreate(&ctx->ev_stop[slot]));
@@ -791,14 +652,14 @@ int origin_timer_start(origin_ctx *ctx, int slot) {
 
 int origin_timer_stop(origin_ctx *ctx, int slot) {
   ORIGIN_USE(ctx);
-  ORIGIN_CHECK_ARG(slot >= 0 && slot < 64 && ctx->ev_made[slot], "timer slot not started");
+  ORIGIN_CHECK_ARG(slot >= 0 && slot < ORIGIN_TIMER_SLOTS && ctx->ev_made[slot], "timer slot not started");
   ORIGIN_HIP(hipEventRecord(ctx->ev_stop[slot], ctx->stream));
   return ORIGIN_OK;
 }
 
 int origin_timer_ms(origin_ctx *ctx, int slot, float *ms) {
   ORIGIN_USE(ctx);
-  ORIGIN_CHECK_ARG(slot >= 0 && slot < 64 && ctx->ev_made[slot] && ms, "timer slot not started");
+  ORIGIN_CHECK_ARG(slot >= 0 && slot < ORIGIN_TIMER_SLOTS && ctx->ev_made[slot] && ms, "timer slot not started");
   ORIGIN_HIP(hipEventSynchronize(ctx->ev_stop[slot]));
   ORIGIN_HIP(hipEventElapsedTime(ms, ctx->ev_start[slot], ctx->ev_stop[slot]));
   return ORIGIN_OK;

@@ -48,7 +48,7 @@ int make_ctab(origin_ctx *ctx, int Nz, int order, double **d_tab) {
   if (ctx->ctab) {
     ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
     // (a continuum pass on the auxiliary stream may still be reading the table)
-    if (ctx->aux_stream && ctx->aux_pending) ORIGIN_HIP(hipStreamSynchronize(ctx->aux_stream));
+    if (int rc = origin_fork_wait(ctx->aux)) return rc;
     ORIGIN_HIP(hipFree(ctx->ctab));
     ctx->ctab = nullptr;
   }
@@ -1109,14 +1109,14 @@ static int dct_cont_std_on(origin_ctx *ctx, bool aux, const float *d_var, const 
   double *part = nullptr;
   if (d_ima_dct) {
     void *scr = nullptr;  // (the aux stream has a scratch of its own: the PCA uses the main one)
-    rc = aux ? origin_aux_scratch(ctx, (size_t)nzc * S * sizeof(double), &scr)
+    rc = aux ? origin_grow(ctx->aux_scratch, (size_t)nzc * S * sizeof(double), ctx->aux.stream, &scr)
              : origin_scratch(ctx, (size_t)nzc * S * sizeof(double), &scr);
     if (rc) return rc;
     part = (double *)scr;
   }
   dim3 grid(cdiv(S, 256), nzc);
-  if (aux && (rc = origin_aux_begin(ctx))) return rc;
-  hipStream_t st = aux ? ctx->aux_stream : ctx->stream;
+  if (aux && (rc = origin_fork_begin(ctx, ctx->aux, origin_make_aux_stream))) return rc;
+  hipStream_t st = aux ? ctx->aux.stream : ctx->stream;
   {
     ProfScope ps(ctx, K_DCT_CONTINUUM, aux ? 3 : 1);  // (events of the main stream: sync form only)
 #define CALL(O)                                                                              \
@@ -1131,7 +1131,7 @@ static int dct_cont_std_on(origin_ctx *ctx, bool aux, const float *d_var, const 
       ORIGIN_LAUNCH_CHECK();
     }
   }
-  if (aux && (rc = origin_aux_end(ctx))) return rc;
+  if (aux && (rc = origin_fork_end(ctx->aux))) return rc;
   return ORIGIN_OK;
 }
 

@@ -155,8 +155,8 @@ int origin_glr_run_rect(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cub
     if (int rc = zero_pads(ctx, pl, d_work, work)) return rc;
   // the launch functions enqueue on ctx->stream: the side stream takes its place for this band
   if (side) {
-    if (int rc = origin_side_begin(ctx)) return rc;
-    std::swap(ctx->stream, ctx->side_stream);
+    if (int rc = origin_fork_begin(ctx, ctx->side, origin_make_side_stream)) return rc;
+    std::swap(ctx->stream, ctx->side.stream);
   }
   int rc = ORIGIN_OK;
   {
@@ -174,8 +174,8 @@ int origin_glr_run_rect(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cub
     rc = origin_spectral_mfma_launch(ctx, a);
   }
   if (side) {
-    std::swap(ctx->stream, ctx->side_stream);
-    if (rc == ORIGIN_OK) rc = origin_side_end(ctx);
+    std::swap(ctx->stream, ctx->side.stream);
+    if (rc == ORIGIN_OK) rc = origin_fork_end(ctx->side);
   }
   return rc;
 }
@@ -184,7 +184,7 @@ int origin_glr_run_finish(origin_ctx *ctx, origin_glr_plan *pl, float *d_work, f
                           float *d_minmap) {
   ORIGIN_USE(ctx);
   ORIGIN_CHECK_ARG(pl && pl->ctx == ctx && d_work, "bad argument");
-  if (int rc = origin_side_join(ctx)) return rc;  // bands on the side stream
+  if (int rc = origin_fork_join(ctx, ctx->side)) return rc;  // bands on the side stream
   if (!d_maxmap && !d_minmap) return ORIGIN_OK;
   const long S = (long)pl->Ny * pl->Nx;
   GlrSpectralIO io = {};

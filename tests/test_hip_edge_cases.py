@@ -510,3 +510,155 @@ def test_allocation_cache_reuses_released_blocks():
     e = ctx.empty((n,), np.float32)
     assert e.ptr == p and sp != p
     ctx.close()
+
+
+# ---- host copies through the pinned staging buffers: 64 MiB chunks, 1 MiB pieces, staged from 32 MiB
+MiB = 1 << 20
+CVT_CHUNK = 16 << 20          # elements of a conversion's chunk (64 MiB of float32)
+
+
+@pytest.fixture(scope="module")
+def ramp251():
+    """arange(n) % 251 as uint8: a piece or a chunk that lands at another offset changes the data."""
+    n = 128 * MiB
+    return np.tile(np.arange(251, dtype=np.uint8), n // 251 + 1)[:n]
+
+
+@pytest.fixture(scope="module")
+def doubles():
+    """float64 values that float32 does not hold: the narrowing rounds every one of them."""
+    return np.random.default_rng(16).standard_normal(2 * CVT_CHUNK) * 1e3
+
+
+@pytest.mark.parametrize("n", [32 * MiB - 1, 32 * MiB, 64 * MiB, 64 * MiB + 1, 128 * MiB])
+def test_plain_copies_at_the_staging_boundaries(ctx, ramp251, n):
+    """upload / to_host of 32 MiB - 1 (the direct copy), 32 MiB (the first staged size: one partial
+    chunk), one whole chunk, one chunk and a byte, two chunks.  Each direction is also checked
+    against direct copies of 16 MiB parts, so that two equal mistakes cannot cancel."""
+    host = ramp251[:n]
+    part = 16 * MiB
+    d = ctx.empty((n,), np.uint8)
+    d.fill_bytes(0xee)
+    d.upload(host)
+    for o in range(0, n, part):
+        m = min(part, n - o)
+        assert np.array_equal(d.view(o, (m,)).to_host(), host[o:o + m]), ("upload", o)
+    assert np.array_equal(d.to_host(), host)
+    d.fill_bytes(0xee)
+    for o in range(0, n, part):
+        m = min(part, n - o)
+        d.view(o, (m,)).upload(host[o:o + m])
+    assert np.array_equal(d.to_host(), host)
+    d.free()
+
+
+@pytest.mark.parametrize("n", [CVT_CHUNK, CVT_CHUNK + 1, 2 * CVT_CHUNK])
+def test_conversions_at_the_chunk_boundaries(ctx, doubles, n):
+    """to_device(float64 -> float32) and to_host_f64 of one chunk, one chunk and an element, two
+    chunks: exactly NumPy's astype."""
+    host = doubles[:n]
+    want = host.astype(np.float32)
+    d = ctx.to_device(host, np.float32)
+    assert d.dtype == np.float32
+    assert np.array_equal(d.to_host(), want)
+    assert np.array_equal(d.to_host_f64(), want.astype(np.float64))
+    d.free()
+
+
+def test_staged_copies_back_to_back_on_one_context(doubles):
+    """A narrowing upload, the widening download of its result, a plain staged download and a plain
+    staged upload, one behind the other on a fresh context: they share two staging buffers and
+    two events, and each direction meets what the other left pending on them."""
+    from origin_amd.device import Context
+    ctx = Context(0)
+    n = CVT_CHUNK + 1
+    host = doubles[:n]
+    want = host.astype(np.float32)
+    d = ctx.to_device(host, np.float32)
+    wide = d.to_host_f64()
+    plain = d.to_host()
+    e = ctx.empty((n,), np.float32)
+    e.upload(plain[::-1])
+    back = e.to_host()
+    assert np.array_equal(wide, want.astype(np.float64))
+    assert np.array_equal(plain, want)
+    assert np.array_equal(back, want[::-1])
+    ctx.close()
+
+
+# ---- the auxiliary stream: origin_dct_cont_std_async at (64, 64, 65), order 3 -- its cont_dct is
+# just over 1 MiB, the smallest block the allocation cache keeps
+AUX_SHAPE, AUX_ORDER = (64, 64, 65), 3
+
+
+def _aux_pass_inputs(ctx):
+    from origin_amd import kernels
+    rng = np.random.default_rng(64)
+    raw = ctx.to_device(rng.standard_normal(AUX_SHAPE, dtype=np.float32) * 3 + 50)
+    var = ctx.to_device(1 + rng.random(AUX_SHAPE, dtype=np.float32))
+    mask = ctx.to_device(np.zeros(AUX_SHAPE, np.uint8))
+    coef = kernels.dct_fit(ctx, raw, var, mask, AUX_ORDER)
+    return var, coef, (raw, mask)     # (kept alive: nothing of theirs goes to the cache meanwhile)
+
+
+def test_reads_wait_for_the_auxiliary_stream_without_a_join(ctx):
+    """to_host of cont_dct / ima_dct of an auxiliary-stream pass, without aux_join: the bits of the
+    synchronous form; aux_join and sync afterwards succeed."""
+    from origin_amd import kernels
+    var, coef, keep = _aux_pass_inputs(ctx)
+    sync_form = kernels.dct_cont_std(ctx, var, coef)
+    want = {k: sync_form[k].to_host() for k in ("cont_dct", "ima_dct")}
+    got = kernels.dct_cont_std(ctx, var, coef, aux=True)
+    for k in ("cont_dct", "ima_dct"):
+        assert np.array_equal(got[k].to_host(), want[k], equal_nan=True), k
+    ctx.aux_join()
+    ctx.sync()
+
+
+def test_free_with_auxiliary_work_pending():
+    """cont_dct freed while the pass that writes it is pending: the cache hands the block to the
+    next request of its size, ordered behind that pass -- what is written next is what is read."""
+    from origin_amd import kernels
+    from origin_amd.device import Context
+    ctx = Context(0)
+    var, coef, keep = _aux_pass_inputs(ctx)
+    cont = ctx.empty(AUX_SHAPE, np.float32)
+    ima = ctx.empty(AUX_SHAPE[1:], np.float32)
+    assert cont.nbytes >= MiB
+    kernels.dct_cont_std(ctx, var, coef, cont_dct=cont, ima_dct=ima, aux=True)
+    p = cont.ptr
+    cont.free()
+    again = ctx.empty(AUX_SHAPE, np.float32)
+    assert again.ptr == p
+    again.fill_bytes(0x3f)
+    assert np.all(again.to_host().view(np.uint8) == 0x3f)
+    again.free()
+    ctx.close()
+
+
+def test_close_with_auxiliary_work_pending():
+    """A context that has made both the side stream (one rectangle of a GLR on it) and the auxiliary
+    stream is closed while auxiliary work is pending; a fresh context then works."""
+    from origin_amd import kernels
+    from origin_amd.device import Context
+    ctx = Context(0)
+    shape = (96, 27, 31)
+    rng = np.random.default_rng(27)
+    plan = kernels.GLRPlan(ctx, shape, synth.moffat_psf(shape[0], 9).astype(np.float64), None,
+                           synth.dico_fwhm(3), 1e-8, True, precision="f16x2")
+    assert plan.rows_supported()
+    cube = ctx.to_device(rng.standard_normal(shape, dtype=np.float32))
+    mask = ctx.to_device(np.zeros(shape, np.uint8))
+    correl, cmin = ctx.empty(shape, np.float32), ctx.empty(shape, np.float32)
+    prof_i = ctx.empty(shape, np.uint8)
+    plan.run_rect(cube, mask, correl, prof_i, cmin, 0, shape[1], 0, shape[2], first=True, side=True)
+    plan.run_finish(want_maps=False)
+    ctx.sync()
+    plan.close()
+    var, coef, keep = _aux_pass_inputs(ctx)
+    out = kernels.dct_cont_std(ctx, var, coef, aux=True)
+    ctx.close()
+    fresh = Context(0)
+    a = np.arange(1000, dtype=np.float32)
+    assert np.array_equal(fresh.to_device(a).to_host(), a)
+    fresh.close()
