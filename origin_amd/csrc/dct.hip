@@ -23,6 +23,12 @@
 // of 77 Gram/RHS entries, then solves the (order+1)^2 SPD system by an in-register
 // Cholesky.  Everything is accumulated in float64: the fit is HBM-bound (9 B/voxel
 // against 43 DFMA/voxel), so exact-ish arithmetic is free.
+//
+// Host side (behind the kernels).  Every entry point starts with dct_begin (shape and order, its
+// own pointers, the cached cosine table) and reaches the kernels' ORDER template parameter through
+// with_order, which calls a generic lambda holding the launches.  The launch geometry has names:
+// fit_plan / FitScratch for the fit, channel_chunks / pair_chunks for the kernels that split the
+// spectral axis over grid.y.
 #include <cmath>
 #include <vector>
 
@@ -69,11 +75,6 @@ int make_ctab(origin_ctx *ctx, int Nz, int order, double **d_tab) {
   return ORIGIN_OK;
 }
 
-struct CtabGuard {  // the table is cached in the context; nothing to release per call
-  double *p = nullptr;
-  explicit CtabGuard(origin_ctx *) {}
-};
-
 // ------------------------------------------------------------------------------------
 // pass 1: moments + solve.  block = (64 lanes, ZS waves); wave w marches z = w, w+ZS, ...
 // The weighted fit needs the 2*ORDER+1 moments M_k and the ORDER+1 weighted projections Rw;
@@ -94,15 +95,13 @@ struct CtabGuard {  // the table is cached in the context; nothing to release pe
 // bytes.  Tried and measured slower or equal: an LDS-DMA ring (`global_load_lds_*` eight rows
 // ahead: M0 / SALU overhead per row), batches of 2, 4 and 16 rows, the table row pinned in the
 // scalar cache (-4 %: the scalar loads are not the limit on their own).
-__device__ __forceinline__ double wave_sum_d64(double v) {
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
 
-#ifndef MOM_BATCH
-#define MOM_BATCH 8
-#endif
+constexpr int MOM_BATCH = 8;   // rows requested back to back (2, 4 and 16 measured: see above)
 constexpr int MOM_PITCH = 68;  // floats per row of the wave's transpose buffer (FOLD)
 constexpr int MOM_TR_FLOATS = 16 * MOM_PITCH;
 
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(512) void dct_moments_kernel(const float *__restric
 #pragma unroll
     for (int a = 0; a < NA; ++a) Rw[a] = fma(wr, ct[a], Rw[a]);
     if constexpr (FOLD) {
-      const double sum = wave_sum_d64((mk || !live) ? 0.0 : (double)r);
+      const double sum = wave_sum((mk || !live) ? 0.0 : (double)r);
       if (lane == 0) part[(long)blockIdx.x * Nz + zm] = sum;
     }
   }
@@ -478,12 +477,6 @@ __global__ __launch_bounds__(256) void dct_continuum_kernel(const double *__rest
 // so the plane reduction only touches raw + mask (5 B/voxel); coefficients are gathered
 // for masked voxels only.  One block reduces `SPB` spaxels of one channel.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <int ORDER, bool VEC>
 __global__ __launch_bounds__(256) void dct_plane_sums_kernel(
     const float *__restrict__ raw, const uint8_t *__restrict__ mask,
@@ -555,6 +548,15 @@ __global__ __launch_bounds__(1024) void coef_total_kernel(const double *__restri
   }
 }
 
+// sum_a Ctot_a cos(a theta_z): the continuum of channel z summed over ALL spaxels
+template <int ORDER>
+__device__ __forceinline__ double ctot_cont(const double *ctot, const double *ct) {
+  double call = 0.0;
+#pragma unroll
+  for (int a = 0; a <= ORDER; ++a) call = fma(ctot[a], ct[a], call);
+  return call;
+}
+
 template <int ORDER>
 __global__ __launch_bounds__(256) void dct_zsum_final_kernel(const double *__restrict__ part,
                                                              const double *__restrict__ ctot,
@@ -562,7 +564,6 @@ __global__ __launch_bounds__(256) void dct_zsum_final_kernel(const double *__res
                                                              int Nz, int nchunk,
                                                              double *__restrict__ zsum,
                                                              double *__restrict__ zcnt) {
-  constexpr int NA = ORDER + 1;
   constexpr int NK = 2 * ORDER + 1;
   const int z = blockIdx.x * 256 + threadIdx.x;
   if (z >= Nz) return;
@@ -571,11 +572,7 @@ __global__ __launch_bounds__(256) void dct_zsum_final_kernel(const double *__res
     sum += part[((long)z * nchunk + c) * 2];
     cnt += part[((long)z * nchunk + c) * 2 + 1];
   }
-  const double *ct = ctab + (long)z * NK;
-  double call = 0.0;
-#pragma unroll
-  for (int a = 0; a < NA; ++a) call = fma(ctot[a], ct[a], call);
-  zsum[z] = sum - call;
+  zsum[z] = sum - ctot_cont<ORDER>(ctot, ctab + (long)z * NK);
   zcnt[z] = cnt;
 }
 
@@ -655,7 +652,6 @@ __global__ __launch_bounds__(256) void dct_zsum_fold_final_kernel(
     const double *__restrict__ slab, int nslab, const double *__restrict__ ctot,
     const double *__restrict__ ctab, int Nz, long S, double *__restrict__ zsum,
     double *__restrict__ zcnt) {
-  constexpr int NA = ORDER + 1;
   constexpr int NK = 2 * ORDER + 1;
   const int z = blockIdx.x * 256 + threadIdx.x;
   if (z >= Nz) return;
@@ -664,11 +660,7 @@ __global__ __launch_bounds__(256) void dct_zsum_fold_final_kernel(
     sum += slab[((long)c * Nz + z) * 2];
     nm += slab[((long)c * Nz + z) * 2 + 1];
   }
-  const double *ct = ctab + (long)z * NK;
-  double call = 0.0;
-#pragma unroll
-  for (int a = 0; a < NA; ++a) call = fma(ctot[a], ct[a], call);
-  zsum[z] = sum - call;
+  zsum[z] = sum - ctot_cont<ORDER>(ctot, ctab + (long)z * NK);
   zcnt[z] = (double)S - nm;
 }
 
@@ -836,37 +828,92 @@ __global__ __launch_bounds__(256) void o2_final_kernel(const double *__restrict_
   out[s] = acc / (double)Nz;
 }
 
-int pick_zchunks(origin_ctx *ctx, long S, int Nz) {
+// ------------------------------------------------------------------------------------
+// host side: launch geometry
+// ------------------------------------------------------------------------------------
+int pick_zchunks(int num_cu, long S, int Nz) {
   // aim for >= 32 blocks of 256 threads per CU: several rounds of blocks, so that the last,
   // partly filled round is a small part of the pass (3681 x 600 x 600: 2 chunks 3.93 ms, 4-16
   // chunks 3.53-3.55 ms, 32 chunks 3.65 ms)
   const long blocks = (S + 255) / 256;
-  long want = ((long)ctx->num_cu * 32 + blocks - 1) / blocks;
+  long want = ((long)num_cu * 32 + blocks - 1) / blocks;
   if (want < 1) want = 1;
   if (want > 64) want = 64;
   if (want > Nz) want = Nz;
   return (int)want;
 }
 
-#define DISPATCH_ORDER(order, CALL)              \
-  switch (order) {                               \
-    case 1: { CALL(1); } break;                  \
-    case 2: { CALL(2); } break;                  \
-    case 3: { CALL(3); } break;                  \
-    case 4: { CALL(4); } break;                  \
-    case 5: { CALL(5); } break;                  \
-    case 6: { CALL(6); } break;                  \
-    case 7: { CALL(7); } break;                  \
-    case 8: { CALL(8); } break;                  \
-    case 9: { CALL(9); } break;                  \
-    case 10: { CALL(10); } break;                \
-    case 11: { CALL(11); } break;                \
-    case 12: { CALL(12); } break;                \
-    default:                                     \
-      origin_set_error("dct order %d unsupported (1..%d)", order, kMaxOrder); \
-      return ORIGIN_E_ARG;                       \
-  }
+// grid.y of the kernels that march a part of the spectral axis: nzc chunks of zchunk items
+struct ZChunks {
+  int zchunk, nzc;
+};
 
+ZChunks split_chunks(int n, int want) {
+  const int zchunk = cdiv(n, want);
+  return {zchunk, cdiv(n, zchunk)};
+}
+
+// chunks of channels (continuum, O2)
+ZChunks channel_chunks(int num_cu, long S, int Nz) {
+  return split_chunks(Nz, pick_zchunks(num_cu, S, Nz));
+}
+
+// chunks of mirror PAIRS of channels (standardise, cont_std)
+ZChunks pair_chunks(int num_cu, long S, int Nz) {
+  return split_chunks(std::max(1, Nz / 2), pick_zchunks(num_cu, S, Nz));
+}
+
+// The fit's geometry.  block = (64, ZS), grid = (waves, nzc) for the moments pass and (waves) for
+// dct_r0_kernel; lds / lds_r0 are their dynamic LDS.
+struct FitPlan {
+  long waves;  // 64-spaxel groups
+  int ZS;      // waves of a block: the z-split of a group
+  int nzc, zchunk;  // chunks of mirror pairs of the moments pass, pairs per chunk
+  int nslab;   // slabs of GSLAB groups (dct_part_reduce_kernel)
+  size_t lds, lds_r0;
+};
+
+FitPlan fit_plan(int num_cu, long S, int Nz, int order, bool fold) {
+  FitPlan g;
+  // z-split so that small fields still fill the chip: waves = S/64 * ZS >= ~4 per SIMD
+  g.waves = (S + 63) / 64;
+  g.ZS = 1;
+  while (g.ZS < 8 && g.waves * g.ZS < (long)num_cu * 16) g.ZS *= 2;
+  const int NACC = (2 * order + 1) + (order + 1);
+  while (g.ZS > 1 && (size_t)(g.ZS - 1) * (NACC + 1) * 64 * sizeof(double) > 64 * 1024) g.ZS /= 2;
+  g.lds = (fold ? (size_t)g.ZS * MOM_TR_FLOATS * sizeof(float) : 0) +
+          (size_t)(g.ZS - 1) * (NACC + 1) * 64 * sizeof(double);
+  g.lds_r0 = (size_t)(g.ZS - 1) * (order + 1) * 64 * sizeof(double);
+  g.nslab = cdiv((int)g.waves, GSLAB);
+  // channel chunks of the moments pass: ~10 rounds of blocks (4 waves per SIMD), chunks >= 256
+  // rows (measured at 3681 x 600 x 600: 2 chunks 3.55 ms, 4: 3.47, 8: 3.21, 12: 3.17)
+  int nzc = (int)((10L * num_cu * 16 + g.waves * g.ZS - 1) / (g.waves * g.ZS));
+  nzc = std::max(1, std::min(std::min(nzc, 16), Nz / 256));
+  // (chunks of mirror PAIRS of channels: whole trips of 8 pairs = 16 rows of every wave)
+  const int npair = std::max(1, Nz / 2);
+  g.zchunk = cdiv(cdiv(npair, nzc), 8 * g.ZS) * 8 * g.ZS;
+  g.nzc = cdiv(npair, g.zchunk);
+  return g;
+}
+
+// the fit's scratch block, as byte offsets:
+// mom | need | part [groups][Nz] | slab [nslab][Nz][2] | ctot | nmask [groups][Nz]
+// (part, slab and nmask are empty without the fold)
+struct FitScratch {
+  size_t mom, need, part, slab, ctot, nmask, end;
+  FitScratch(const FitPlan &g, long S, int Nz, int order, bool fold) {
+    const int NACC = (2 * order + 1) + (order + 1);
+    mom = 0;
+    need = mom + (size_t)g.nzc * (NACC + 1) * S * sizeof(double);
+    part = need + (((size_t)S + 7) & ~(size_t)7);
+    slab = part + (fold ? (size_t)g.waves * Nz * sizeof(double) : 0);
+    ctot = slab + (fold ? (size_t)g.nslab * Nz * 2 * sizeof(double) : 0);
+    nmask = ctot + 64 * sizeof(double);
+    end = nmask + (fold ? (size_t)g.waves * Nz : 0);
+  }
+};
+
+// ---- what every entry point does before its first launch, and the order dispatch
 int check_dims(int Nz, int Ny, int Nx, int order) {
   ORIGIN_CHECK_ARG(Nz > 0 && Ny > 0 && Nx > 0, "bad cube shape (%d,%d,%d)", Nz, Ny, Nx);
   ORIGIN_CHECK_ARG(order >= 1 && order <= kMaxOrder, "dct order %d unsupported (1..%d)", order,
@@ -875,92 +922,103 @@ int check_dims(int Nz, int Ny, int Nx, int order) {
   return ORIGIN_OK;
 }
 
-}  // namespace
+struct DctCall {
+  long S = 0;              // spaxels
+  double *ctab = nullptr;  // the context's cosine table for (Nz, order)
+};
 
-extern "C" {
+// shape and order, then the entry point's own pointers (`pointers`: all of them given), then the
+// table: in this order, so that a bad call gets the same error from every entry point
+int dct_begin(origin_ctx *ctx, int Nz, int Ny, int Nx, int order, bool pointers, DctCall *c) {
+  if (int rc = check_dims(Nz, Ny, Nx, order)) return rc;
+  ORIGIN_CHECK_ARG(pointers, "null pointer");
+  c->S = (long)Ny * Nx;
+  return make_ctab(ctx, Nz, order, &c->ctab);
+}
+
+// The run-time order -> the ORDER template parameter of the kernels: f(integral_constant<int, O>)
+// does the launches of order = O in 1..kMaxOrder and the launch check follows; any other order is
+// an argument error.
+template <typename F>
+int with_order(int order, F f) {
+  static_assert(kMaxOrder == 12, "one case per order");
+  switch (order) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 9: f(std::integral_constant<int, 9>{}); break;
+    case 10: f(std::integral_constant<int, 10>{}); break;
+    case 11: f(std::integral_constant<int, 11>{}); break;
+    case 12: f(std::integral_constant<int, 12>{}); break;
+    default:
+      origin_set_error("dct order %d unsupported (1..%d)", order, kMaxOrder);
+      return ORIGIN_E_ARG;
+  }
+  ORIGIN_LAUNCH_CHECK();
+  return ORIGIN_OK;
+}
 
 // fit (+ the per-channel residual sums when d_zsum is given: origin_dct_fit_sums)
-static int dct_fit_impl(origin_ctx *ctx, const float *d_raw, const float *d_var,
-                        const uint8_t *d_mask, int Nz, int Ny, int Nx, int order, int approx,
-                        double *d_coef, double *d_zsum, double *d_zcnt) {
+int dct_fit_impl(origin_ctx *ctx, const float *d_raw, const float *d_var, const uint8_t *d_mask,
+                 int Nz, int Ny, int Nx, int order, int approx, double *d_coef, double *d_zsum,
+                 double *d_zcnt) {
   ORIGIN_USE(ctx);
-  int rc = check_dims(Nz, Ny, Nx, order);
+  DctCall c;
+  int rc = dct_begin(ctx, Nz, Ny, Nx, order, d_raw && d_var && d_mask && d_coef, &c);
   if (rc) return rc;
-  ORIGIN_CHECK_ARG(d_raw && d_var && d_mask && d_coef, "null pointer");
-  const long S = (long)Ny * Nx;
-  CtabGuard tab(ctx);
-  rc = make_ctab(ctx, Nz, order, &tab.p);
-  if (rc) return rc;
+  const long S = c.S;
   const bool fold = d_zsum != nullptr;
-  // z-split so that small fields still fill the chip: waves = S/64 * ZS >= ~4 per SIMD
-  const long waves = (S + 63) / 64;
-  int ZS = 1;
-  while (ZS < 8 && waves * ZS < (long)ctx->num_cu * 16) ZS *= 2;
-  const int NACC = (2 * order + 1) + (order + 1);
-  while (ZS > 1 && (size_t)(ZS - 1) * (NACC + 1) * 64 * sizeof(double) > 64 * 1024) ZS /= 2;
-  const size_t lds = (fold ? (size_t)ZS * MOM_TR_FLOATS * sizeof(float) : 0) +
-                     (size_t)(ZS - 1) * (NACC + 1) * 64 * sizeof(double);
-  const size_t lds_r0 = (size_t)(ZS - 1) * (order + 1) * 64 * sizeof(double);
-  // scratch: mom | need | part [groups][Nz] | slab [nslab][Nz][2] | ctot | nmask [groups][Nz]
-  const int nslab = cdiv((int)waves, GSLAB);
-  // channel chunks of the moments pass: ~10 rounds of blocks (4 waves per SIMD), chunks >= 256
-  // rows (measured at 3681 x 600 x 600: 2 chunks 3.55 ms, 4: 3.47, 8: 3.21, 12: 3.17)
-  int nzc = (int)((10L * ctx->num_cu * 16 + waves * ZS - 1) / (waves * ZS));
-  nzc = std::max(1, std::min(std::min(nzc, 16), Nz / 256));
-  // (chunks of mirror PAIRS of channels: whole trips of 8 pairs = 16 rows of every wave)
-  const int npair = std::max(1, Nz / 2);
-  const int zchunk = cdiv(cdiv(npair, nzc), 8 * ZS) * 8 * ZS;
-  nzc = cdiv(npair, zchunk);
-  dim3 grid((unsigned)waves), gridm((unsigned)waves, nzc), block(64, ZS);
-  const size_t mom_bytes = (size_t)nzc * (NACC + 1) * S * sizeof(double);
-  const size_t need_bytes = ((size_t)S + 7) & ~(size_t)7;
-  const size_t part_bytes = fold ? (size_t)waves * Nz * sizeof(double) : 0;
-  const size_t slab_bytes = fold ? (size_t)nslab * Nz * 2 * sizeof(double) : 0;
-  const size_t nm_bytes = fold ? (size_t)waves * Nz : 0;
-  void *scr = nullptr;
-  rc = origin_scratch(ctx, mom_bytes + need_bytes + part_bytes + slab_bytes + 64 * sizeof(double) +
-                               nm_bytes, &scr);
+  const FitPlan g = fit_plan(ctx->num_cu, S, Nz, order, fold);
+  const FitScratch at(g, S, Nz, order, fold);
+  void *base = nullptr;
+  rc = origin_scratch(ctx, at.end, &base);
   if (rc) return rc;
-  double *mom = (double *)scr;
-  uint8_t *need = (uint8_t *)scr + mom_bytes;
-  double *part = (double *)((char *)scr + mom_bytes + need_bytes);
-  double *slab = (double *)((char *)part + part_bytes);
-  double *ctot = (double *)((char *)slab + slab_bytes);
-  uint8_t *nmask = (uint8_t *)(ctot + 64);
+  char *scr = (char *)base;
+  double *mom = (double *)(scr + at.mom), *part = (double *)(scr + at.part);
+  double *slab = (double *)(scr + at.slab), *ctot = (double *)(scr + at.ctot);
+  uint8_t *need = (uint8_t *)(scr + at.need), *nmask = (uint8_t *)(scr + at.nmask);
+  const dim3 grid((unsigned)g.waves), gridm((unsigned)g.waves, g.nzc), block(64, g.ZS);
   {
     ProfScope ps(ctx, K_DCT_FIT);
-    if (fold) ORIGIN_HIP(hipMemsetAsync(nmask, 0, nm_bytes, ctx->stream));
-#define CALL(O)                                                                                  \
-  if (fold)                                                                                      \
-    hipLaunchKernelGGL((dct_moments_kernel<O, true>), gridm, block, lds, ctx->stream, d_raw,     \
-                       d_var, d_mask, tab.p, Nz, S, zchunk, mom, part);                          \
-  else if (!approx)                                                                              \
-    hipLaunchKernelGGL((dct_moments_kernel<O, false>), gridm, block, lds, ctx->stream, d_raw,    \
-                       d_var, d_mask, tab.p, Nz, S, zchunk, mom, (double *)nullptr);             \
-  hipLaunchKernelGGL(dct_solve_kernel<O>, dim3(cdiv(S, 256)), dim3(256), 0, ctx->stream, mom,    \
-                     nzc, S, approx, d_coef, need);                                              \
-  hipLaunchKernelGGL(dct_r0_kernel<O>, grid, block, lds_r0, ctx->stream, d_raw, need, tab.p,     \
-                     Nz, S, d_coef)
-    DISPATCH_ORDER(order, CALL)
-#undef CALL
-    ORIGIN_LAUNCH_CHECK();
+    if (fold) ORIGIN_HIP(hipMemsetAsync(nmask, 0, at.end - at.nmask, ctx->stream));
+    rc = with_order(order, [&](auto o) {
+      constexpr int O = decltype(o)::value;
+      if (fold)
+        hipLaunchKernelGGL((dct_moments_kernel<O, true>), gridm, block, g.lds, ctx->stream, d_raw,
+                           d_var, d_mask, c.ctab, Nz, S, g.zchunk, mom, part);
+      else if (!approx)
+        hipLaunchKernelGGL((dct_moments_kernel<O, false>), gridm, block, g.lds, ctx->stream, d_raw,
+                           d_var, d_mask, c.ctab, Nz, S, g.zchunk, mom, (double *)nullptr);
+      hipLaunchKernelGGL(dct_solve_kernel<O>, dim3(cdiv(S, 256)), dim3(256), 0, ctx->stream, mom,
+                         g.nzc, S, approx, d_coef, need);
+      hipLaunchKernelGGL(dct_r0_kernel<O>, grid, block, g.lds_r0, ctx->stream, d_raw, need, c.ctab,
+                         Nz, S, d_coef);
+    });
+    if (rc) return rc;
   }
   if (!fold) return ORIGIN_OK;
   ProfScope ps(ctx, K_DCT_SUMS);
   hipLaunchKernelGGL(coef_total_kernel, dim3(order + 1), dim3(1024), 0, ctx->stream, d_coef, S,
                      ctot);
-#define CALL(O)                                                                                  \
-  hipLaunchKernelGGL(dct_masked_corr_kernel<O>, dim3((unsigned)waves, cdiv(Nz, 64)), dim3(64), 0, \
-                     ctx->stream, d_mask, need, d_coef, tab.p, Nz, S, part, nmask);              \
-  hipLaunchKernelGGL(dct_part_reduce_kernel, dim3(cdiv(Nz, 64), nslab), dim3(256), 0,            \
-                     ctx->stream, part, nmask, Nz, (int)waves, slab);                            \
-  hipLaunchKernelGGL(dct_zsum_fold_final_kernel<O>, dim3(cdiv(Nz, 256)), dim3(256), 0,           \
-                     ctx->stream, slab, nslab, ctot, tab.p, Nz, S, d_zsum, d_zcnt)
-  DISPATCH_ORDER(order, CALL)
-#undef CALL
-  ORIGIN_LAUNCH_CHECK();
-  return ORIGIN_OK;
+  return with_order(order, [&](auto o) {
+    constexpr int O = decltype(o)::value;
+    hipLaunchKernelGGL(dct_masked_corr_kernel<O>, dim3((unsigned)g.waves, cdiv(Nz, 64)), dim3(64),
+                       0, ctx->stream, d_mask, need, d_coef, c.ctab, Nz, S, part, nmask);
+    hipLaunchKernelGGL(dct_part_reduce_kernel, dim3(cdiv(Nz, 64), g.nslab), dim3(256), 0,
+                       ctx->stream, part, nmask, Nz, (int)g.waves, slab);
+    hipLaunchKernelGGL(dct_zsum_fold_final_kernel<O>, dim3(cdiv(Nz, 256)), dim3(256), 0,
+                       ctx->stream, slab, g.nslab, ctot, c.ctab, Nz, S, d_zsum, d_zcnt);
+  });
 }
+
+}  // namespace
+
+extern "C" {
 
 int origin_dct_fit(origin_ctx *ctx, const float *d_raw, const float *d_var,
                    const uint8_t *d_mask, int Nz, int Ny, int Nx, int order, int approx,
@@ -986,37 +1044,26 @@ int origin_dct_fit_sums(origin_ctx *ctx, const float *d_raw, const float *d_var,
 int origin_dct_continuum(origin_ctx *ctx, const double *d_coef, int Nz, int Ny, int Nx,
                          int order, float *d_cont) {
   ORIGIN_USE(ctx);
-  int rc = check_dims(Nz, Ny, Nx, order);
+  DctCall c;
+  int rc = dct_begin(ctx, Nz, Ny, Nx, order, d_coef && d_cont, &c);
   if (rc) return rc;
-  ORIGIN_CHECK_ARG(d_coef && d_cont, "null pointer");
-  const long S = (long)Ny * Nx;
-  CtabGuard tab(ctx);
-  rc = make_ctab(ctx, Nz, order, &tab.p);
-  if (rc) return rc;
-  const int nzc = pick_zchunks(ctx, S, Nz);
-  const int zchunk = cdiv(Nz, nzc);
-  dim3 grid(cdiv(S, 256), cdiv(Nz, zchunk));
+  const ZChunks ch = channel_chunks(ctx->num_cu, c.S, Nz);
+  dim3 grid(cdiv(c.S, 256), ch.nzc);
   ProfScope ps(ctx, K_DCT_CONTINUUM);
-#define CALL(O)                                                                                \
-  hipLaunchKernelGGL(dct_continuum_kernel<O>, grid, dim3(256), 0, ctx->stream, d_coef, tab.p, \
-                     Nz, S, zchunk, d_cont)
-  DISPATCH_ORDER(order, CALL)
-#undef CALL
-  ORIGIN_LAUNCH_CHECK();
-  return ORIGIN_OK;
+  return with_order(order, [&](auto o) {
+    hipLaunchKernelGGL(dct_continuum_kernel<decltype(o)::value>, grid, dim3(256), 0, ctx->stream,
+                       d_coef, c.ctab, Nz, c.S, ch.zchunk, d_cont);
+  });
 }
 
 int origin_dct_resid_sums(origin_ctx *ctx, const float *d_raw, const uint8_t *d_mask,
                           const double *d_coef, int Nz, int Ny, int Nx, int order,
                           double *d_zsum, double *d_zcnt) {
   ORIGIN_USE(ctx);
-  int rc = check_dims(Nz, Ny, Nx, order);
+  DctCall c;
+  int rc = dct_begin(ctx, Nz, Ny, Nx, order, d_raw && d_mask && d_coef && d_zsum && d_zcnt, &c);
   if (rc) return rc;
-  ORIGIN_CHECK_ARG(d_raw && d_mask && d_coef && d_zsum && d_zcnt, "null pointer");
-  const long S = (long)Ny * Nx;
-  CtabGuard tab(ctx);
-  rc = make_ctab(ctx, Nz, order, &tab.p);
-  if (rc) return rc;
+  const long S = c.S;
   const int spb = 8192;
   const int nchunk = cdiv(S, spb);
   const bool vec = (S & 3) == 0;
@@ -1030,19 +1077,17 @@ int origin_dct_resid_sums(origin_ctx *ctx, const float *d_raw, const uint8_t *d_
   hipLaunchKernelGGL(coef_total_kernel, dim3(order + 1), dim3(1024), 0, ctx->stream, d_coef, S,
                      ctot);
   dim3 grid(nchunk, Nz);
-#define CALL(O)                                                                                \
-  if (vec)                                                                                     \
-    hipLaunchKernelGGL((dct_plane_sums_kernel<O, true>), grid, dim3(256), 0, ctx->stream, d_raw, \
-                       d_mask, d_coef, tab.p, S, spb, part);                                   \
-  else                                                                                         \
-    hipLaunchKernelGGL((dct_plane_sums_kernel<O, false>), grid, dim3(256), 0, ctx->stream,     \
-                       d_raw, d_mask, d_coef, tab.p, S, spb, part);                            \
-  hipLaunchKernelGGL(dct_zsum_final_kernel<O>, dim3(cdiv(Nz, 256)), dim3(256), 0, ctx->stream, \
-                     part, ctot, tab.p, Nz, nchunk, d_zsum, d_zcnt)
-  DISPATCH_ORDER(order, CALL)
-#undef CALL
-  ORIGIN_LAUNCH_CHECK();
-  return ORIGIN_OK;
+  return with_order(order, [&](auto o) {
+    constexpr int O = decltype(o)::value;
+    if (vec)
+      hipLaunchKernelGGL((dct_plane_sums_kernel<O, true>), grid, dim3(256), 0, ctx->stream, d_raw,
+                         d_mask, d_coef, c.ctab, S, spb, part);
+    else
+      hipLaunchKernelGGL((dct_plane_sums_kernel<O, false>), grid, dim3(256), 0, ctx->stream,
+                         d_raw, d_mask, d_coef, c.ctab, S, spb, part);
+    hipLaunchKernelGGL(dct_zsum_final_kernel<O>, dim3(cdiv(Nz, 256)), dim3(256), 0, ctx->stream,
+                       part, ctot, c.ctab, Nz, nchunk, d_zsum, d_zcnt);
+  });
 }
 
 int origin_dct_standardize(origin_ctx *ctx, const float *d_raw, const float *d_var,
@@ -1051,83 +1096,72 @@ int origin_dct_standardize(origin_ctx *ctx, const float *d_raw, const float *d_v
                            int Nx, int order, float *d_cube_std, float *d_cont_dct,
                            float *d_ima_std, float *d_ima_dct, double *d_o2) {
   ORIGIN_USE(ctx);
-  int rc = check_dims(Nz, Ny, Nx, order);
+  DctCall c;
+  int rc = dct_begin(ctx, Nz, Ny, Nx, order,
+                     d_raw && d_var && d_mask && d_coef && d_zsum && d_zcnt && d_cube_std, &c);
   if (rc) return rc;
-  ORIGIN_CHECK_ARG(d_raw && d_var && d_mask && d_coef && d_zsum && d_zcnt && d_cube_std,
-                   "null pointer");
-  const long S = (long)Ny * Nx;
-  CtabGuard tab(ctx);
-  rc = make_ctab(ctx, Nz, order, &tab.p);
-  if (rc) return rc;
-  const int nzc0 = pick_zchunks(ctx, S, Nz);
-  const int npair = std::max(1, Nz / 2);  // the kernel's chunks are of mirror PAIRS of channels
-  const int zchunk = cdiv(npair, nzc0);
-  const int nzc = cdiv(npair, zchunk);
+  const long S = c.S;
+  const ZChunks ch = pair_chunks(ctx->num_cu, S, Nz);
   const bool want = d_ima_std || d_ima_dct || d_o2;
   double *part = nullptr, *zmean = nullptr;
   {
     void *scr = nullptr;
-    const size_t pbytes = want ? (size_t)nzc * 3 * S * sizeof(double) : 0;
+    const size_t pbytes = want ? (size_t)ch.nzc * 3 * S * sizeof(double) : 0;
     rc = origin_scratch(ctx, pbytes + (size_t)Nz * sizeof(double), &scr);
     if (rc) return rc;
     if (want) part = (double *)scr;
     zmean = (double *)((char *)scr + pbytes);
   }
-  dim3 grid(cdiv(S, 256), nzc);
+  dim3 grid(cdiv(S, 256), ch.nzc);
   ProfScope ps(ctx, K_DCT_STANDARDIZE);
   hipLaunchKernelGGL(zmean_kernel, dim3(cdiv(Nz, 256)), dim3(256), 0, ctx->stream, d_zsum, d_zcnt,
                      Nz, zmean);
-#define CALL(O)                                                                               \
-  hipLaunchKernelGGL(dct_standardize_kernel<O>, grid, dim3(256), 0, ctx->stream, d_raw, d_var, \
-                     d_mask, d_coef, tab.p, zmean, Nz, S, zchunk, d_cube_std, d_cont_dct, part)
-  DISPATCH_ORDER(order, CALL)
-#undef CALL
-  ORIGIN_LAUNCH_CHECK();
+  rc = with_order(order, [&](auto o) {
+    hipLaunchKernelGGL(dct_standardize_kernel<decltype(o)::value>, grid, dim3(256), 0, ctx->stream,
+                       d_raw, d_var, d_mask, d_coef, c.ctab, zmean, Nz, S, ch.zchunk, d_cube_std,
+                       d_cont_dct, part);
+  });
+  if (rc) return rc;
   if (want) {
     hipLaunchKernelGGL(std_images_final_kernel, dim3(cdiv(S, 256)), dim3(256), 0, ctx->stream,
-                       part, nzc, S, Nz, d_ima_std, d_ima_dct, d_o2);
+                       part, ch.nzc, S, Nz, d_ima_std, d_ima_dct, d_o2);
     ORIGIN_LAUNCH_CHECK();
   }
   return ORIGIN_OK;
 }
 
+// cont_dct = cont / sqrt(var) on the main stream or, aux, on the auxiliary one
 static int dct_cont_std_on(origin_ctx *ctx, bool aux, const float *d_var, const double *d_coef,
                            int Nz, int Ny, int Nx, int order, float *d_cont_dct,
                            float *d_ima_dct) {
   ORIGIN_USE(ctx);
-  int rc = check_dims(Nz, Ny, Nx, order);
+  DctCall c;
+  int rc = dct_begin(ctx, Nz, Ny, Nx, order, d_var && d_coef && d_cont_dct, &c);
   if (rc) return rc;
-  ORIGIN_CHECK_ARG(d_var && d_coef && d_cont_dct, "null pointer");
-  const long S = (long)Ny * Nx;
-  CtabGuard tab(ctx);
-  rc = make_ctab(ctx, Nz, order, &tab.p);
-  if (rc) return rc;
-  const int nzc0 = pick_zchunks(ctx, S, Nz);
-  const int npair = std::max(1, Nz / 2);  // (chunks of mirror pairs of channels)
-  const int zchunk = cdiv(npair, nzc0);
-  const int nzc = cdiv(npair, zchunk);
+  const long S = c.S;
+  const ZChunks ch = pair_chunks(ctx->num_cu, S, Nz);
   double *part = nullptr;
   if (d_ima_dct) {
     void *scr = nullptr;  // (the aux stream has a scratch of its own: the PCA uses the main one)
-    rc = aux ? origin_grow(ctx->aux_scratch, (size_t)nzc * S * sizeof(double), ctx->aux.stream, &scr)
-             : origin_scratch(ctx, (size_t)nzc * S * sizeof(double), &scr);
+    const size_t bytes = (size_t)ch.nzc * S * sizeof(double);
+    rc = aux ? origin_grow(ctx->aux_scratch, bytes, ctx->aux.stream, &scr)
+             : origin_scratch(ctx, bytes, &scr);
     if (rc) return rc;
     part = (double *)scr;
   }
-  dim3 grid(cdiv(S, 256), nzc);
+  dim3 grid(cdiv(S, 256), ch.nzc);
   if (aux && (rc = origin_fork_begin(ctx, ctx->aux, origin_make_aux_stream))) return rc;
   hipStream_t st = aux ? ctx->aux.stream : ctx->stream;
   {
     ProfScope ps(ctx, K_DCT_CONTINUUM, aux ? 3 : 1);  // (events of the main stream: sync form only)
-#define CALL(O)                                                                              \
-  hipLaunchKernelGGL(dct_cont_std_kernel<O>, grid, dim3(256), 0, st, d_var, d_coef, tab.p, Nz, S, \
-                     zchunk, d_cont_dct, part)
-    DISPATCH_ORDER(order, CALL)
-#undef CALL
-    ORIGIN_LAUNCH_CHECK();
+    rc = with_order(order, [&](auto o) {
+      hipLaunchKernelGGL(dct_cont_std_kernel<decltype(o)::value>, grid, dim3(256), 0, st, d_var,
+                         d_coef, c.ctab, Nz, S, ch.zchunk, d_cont_dct, part);
+    });
+    if (rc) return rc;
     if (d_ima_dct) {
-      hipLaunchKernelGGL(cont_image_final_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, part, nzc,
-                         S, Nz, d_ima_dct);
+      hipLaunchKernelGGL(cont_image_final_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, part,
+                         ch.nzc, S, Nz, d_ima_dct);
       ORIGIN_LAUNCH_CHECK();
     }
   }
@@ -1148,17 +1182,15 @@ int origin_dct_cont_std_async(origin_ctx *ctx, const float *d_var, const double 
 int origin_o2(origin_ctx *ctx, const float *d_cube, int Nz, long S, double *d_out) {
   ORIGIN_USE(ctx);
   ORIGIN_CHECK_ARG(Nz > 0 && S > 0 && d_cube && d_out, "bad arguments");
-  const int nzc0 = pick_zchunks(ctx, S, Nz);
-  const int zchunk = cdiv(Nz, nzc0);
-  const int nzc = cdiv(Nz, zchunk);
+  const ZChunks ch = channel_chunks(ctx->num_cu, S, Nz);
   void *scr = nullptr;
-  int rc = origin_scratch(ctx, (size_t)nzc * S * sizeof(double), &scr);
+  int rc = origin_scratch(ctx, (size_t)ch.nzc * S * sizeof(double), &scr);
   if (rc) return rc;
   ProfScope ps(ctx, K_O2);
-  hipLaunchKernelGGL(o2_partial_kernel, dim3(cdiv(S, 256), nzc), dim3(256), 0, ctx->stream,
-                     d_cube, Nz, S, zchunk, (double *)scr);
+  hipLaunchKernelGGL(o2_partial_kernel, dim3(cdiv(S, 256), ch.nzc), dim3(256), 0, ctx->stream,
+                     d_cube, Nz, S, ch.zchunk, (double *)scr);
   hipLaunchKernelGGL(o2_final_kernel, dim3(cdiv(S, 256)), dim3(256), 0, ctx->stream,
-                     (const double *)scr, nzc, S, Nz, d_out);
+                     (const double *)scr, ch.nzc, S, Nz, d_out);
   ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }

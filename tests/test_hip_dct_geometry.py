@@ -63,8 +63,8 @@ def _cdiv(a, b):
 
 
 def _geometry(Nz, S, order, num_cu=256):
-    """(ZS, zchunk, nzc) as dct_fit_impl picks them on a chip of ``num_cu`` CUs: wave w of chunk c
-    owns the mirror pairs p = c * zchunk + w + i * ZS, pair p = channels p and Nz - 1 - p."""
+    """(ZS, zchunk, nzc) as fit_plan (csrc/dct.hip) picks them on a chip of ``num_cu`` CUs: wave w of
+    chunk c owns the mirror pairs p = c * zchunk + w + i * ZS, pair p = channels p and Nz - 1 - p."""
     waves = _cdiv(S, 64)
     ZS = 1
     while ZS < 8 and waves * ZS < num_cu * 16:
@@ -254,6 +254,67 @@ def test_fit_one_wave_per_group_and_several_chunks(ctx):
     d_c = ctx.to_device(c.reshape(order + 1, 1, len(idx)), np.float64)
     cont = kernels.dct_continuum(ctx, d_c, Nz).to_host().reshape(Nz, len(idx))
     _assert_scaled(cont, cont_ref, 1e-5, "continuum")
+
+
+# ------------------------------------------------------ 2b. every order reaches its own kernels
+ORDERS_SHAPE = (13, 3, 5)
+
+
+@pytest.fixture(scope="module")
+def small_cube(ctx):
+    raw, var, mask = _benign(ORDERS_SHAPE, seed=14)  # (a masked voxel outside the masked spaxel)
+    return raw, var, mask, _upload(ctx, ORDERS_SHAPE, raw, var, mask)
+
+
+def _check_order(ctx, small_cube, order):
+    """dct_fit_sums, dct_continuum and the five outputs of dct_standardize at ``order`` on the whole
+    (13, 3, 5) field against the float64 reference, benign tolerances of the module docstring."""
+    from origin_amd import kernels
+    raw, var, mask, dev = small_cube
+    Nz, S = raw.shape
+    r64, v64 = raw.astype(np.float64), var.astype(np.float64)
+    cont_ref, coef_ref = cpu_ref.dct_fit_columns(r64, v64, mask, order)
+    assert coef_ref.shape == (order + 1, S)
+    coef, zsum, zcnt = kernels.dct_fit_sums(ctx, *dev, order)
+    c = coef.to_host().reshape(order + 1, S)
+    assert np.all(np.abs(c - coef_ref) <= 1e-5 * np.abs(r64).max(axis=0)), (
+        f"order {order}: coefficients off by up to {np.abs(c - coef_ref).max():.3e}")
+    cont = kernels.dct_continuum(ctx, coef, Nz).to_host().reshape(Nz, S)
+    _assert_scaled(cont, cont_ref, 1e-5, f"order {order}: continuum")
+    _check_sums(zsum, zcnt, raw, mask, cont, f"order {order}: fit_sums")
+    std = kernels.dct_standardize(ctx, *dev, coef, zsum, zcnt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        zmean = zsum.to_host() / zcnt.to_host()
+    ref = cpu_ref.standardize_columns(r64, v64, mask, cont_ref, zmean)
+    for k in STD_KEYS:
+        _assert_scaled(std[k].to_host().reshape(ref[k].shape), ref[k], 1e-5, f"order {order}: {k}")
+
+
+@pytest.mark.parametrize("order", range(1, 13))
+def test_every_order_runs_its_own_instantiation(ctx, small_cube, order):
+    """The run-time order selects the kernels' ORDER template parameter (with_order, csrc/dct.hip).
+    The coefficient array has order + 1 rows, so a dispatch that lands on a neighbouring
+    instantiation gives another continuum, not a rounding difference."""
+    _check_order(ctx, small_cube, order)
+
+
+def test_unsupported_orders_raise_and_a_valid_call_still_works(ctx, small_cube):
+    """Order 0, order 13 and order 12 on 12 channels are refused by origin_dct_fit,
+    origin_dct_continuum and origin_dct_standardize; the next valid call gives the right answer."""
+    from origin_amd import _capi, kernels
+    Ny, Nx = ORDERS_SHAPE[1:]
+    for order, Nz in ((0, 13), (13, 13), (12, 12)):
+        raw, var = ctx.zeros((Nz, Ny, Nx), np.float32), ctx.zeros((Nz, Ny, Nx), np.float32)
+        mask = ctx.zeros((Nz, Ny, Nx), np.uint8)
+        coef = ctx.zeros((order + 1, Ny, Nx), np.float64)
+        zsum, zcnt = ctx.zeros((Nz,), np.float64), ctx.zeros((Nz,), np.float64)
+        for call in (lambda: kernels.dct_fit(ctx, raw, var, mask, order),
+                     lambda: kernels.dct_continuum(ctx, coef, Nz),
+                     lambda: kernels.dct_standardize(ctx, raw, var, mask, coef, zsum, zcnt)):
+            with pytest.raises(_capi.OriginHipError) as e:
+                call()
+            assert e.value.code == -1 and "order" in str(e.value), (order, Nz)
+    _check_order(ctx, small_cube, 10)
 
 
 # ------------------------------------------------------------------ 3. mask-flag placement
