@@ -457,6 +457,51 @@ int origin_sparse_zmax_map(origin_ctx *ctx, const long long *d_idx, const float 
                            const int *d_counts, long nseg, int seg_cap, const uint8_t *d_keep,
                            long S, float *d_map);
 
+/* ---- E. line estimation -------------------------------------------------------------
+ * estimation_line (lib_origin.py:1805-1938, called by ComputeSpectra.run, steps.py:1082-1096)
+ * with GridAnalysis (:1620-1790), method_PCA_wgt (:1535-1617), LS_deconv_wgt (:1482-1510),
+ * conv_wgt (:1513-1532) and peakdet (:1793-1801), for `ndet` detections in batches sized from
+ * origin_mem_info (max_problems > 0: at most that many (detection, grid offset) problems per
+ * batch, whole detections; results do not depend on it).  float64 after the gather.
+ *   d_raw, d_var  float32 device cubes (Nz, Ny, Nx);
+ *   h_psf         float64 [nfields][Nz][P][P] (P odd, <= 41); h_weights float64 [nfields][Ny][Nx]
+ *                 or NULL (weights=None).  With weights the PSF of a problem is sum_n w_n[window]
+ *                 psf_n[z] (:1713-1717) and size_grid must be 0;
+ *   h_det         int32 [ndet][3]: z0, y0, x0, inside the cube;
+ *   size_grid     0..5; criteria 0 = 'flux', 1 = 'mse'; order_dct -1 = None (PCA LS only);
+ *   h_line, h_var float64 [ndet][Nz]: estimated line / variance of the winning grid offset;
+ *   h_flux5, h_mse5 float64 [ndet]; h_yxz int32 [ndet][3]: y, x, z; h_status int32 [ndet]: 1 =
+ *                 the fallback row (0.0, 1e6, [0], [0], y0, x0, z0) of :1760-1769 (line / var
+ *                 zero), given where every grid offset is degenerate or the criterion is not finite;
+ *   h_nbatch      (may be NULL) batches run.
+ * Deviations from the reference: a window with a non-finite raw value, a
+ * var that is NaN or <= 0, or a channel whose sum psf^2/var is 0 never reaches the eigen-solver
+ * (fallback row instead of ARPACK on NaN); grid offsets outside the field do not compete; the
+ * first best offset wins a tie.  Synchronises. */
+int origin_lines_estimate(origin_ctx *ctx, const float *d_raw, const float *d_var, int Nz, int Ny,
+                          int Nx, int nfields, int P, const double *h_psf, const double *h_weights,
+                          int ndet, const int *h_det, int size_grid, int criteria, int order_dct,
+                          int horiz_psf, int horiz, int max_problems, double *h_line, double *h_var,
+                          double *h_flux5, double *h_mse5, int *h_yxz, int *h_status,
+                          int *h_nbatch);
+/* Pieces of the above exposed for unit tests.  gather: the standardised, centred work matrices of
+ * :1575-1579 for `nprob` windows centred at h_centres (int32 [nprob][2]: y, x; any position, the
+ * part outside the field is data 0 / var +inf, :1884-1888): d_A float64 [nprob][Nz][ld], ld = P*P
+ * rounded up to 16, slack columns zero; d_mean float64 [nprob][Nz] the row means that were
+ * subtracted; d_flag int32 [nprob]: 1 = degenerate (matrix and means zero).
+ * select: the grid analysis of :1693-1790 on given deconvolutions: h_deconv / h_varest float64
+ * [nprob][Nz] and h_flag int32 [nprob] for the problems of the detections in order -- per
+ * detection its grid offsets inside the field, dy major (np.where order); outputs as above. */
+int origin_lines_gather(origin_ctx *ctx, const float *d_raw, const float *d_var, int Nz, int Ny,
+                        int Nx, int nfields, int P, const double *h_psf, const double *h_weights,
+                        int nprob, const int *h_centres, double *d_A, double *d_mean, int *d_flag);
+int origin_lines_select(origin_ctx *ctx, const float *d_raw, int Nz, int Ny, int Nx, int nfields,
+                        int P, const double *h_psf, const double *h_weights, int ndet,
+                        const int *h_det, int size_grid, int criteria, int horiz_psf, int horiz,
+                        const double *h_deconv, const double *h_varest, const int *h_flag,
+                        double *h_line, double *h_var, double *h_flux5, double *h_mse5, int *h_yxz,
+                        int *h_status);
+
 #ifdef __cplusplus
 }
 #endif

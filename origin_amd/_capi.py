@@ -104,6 +104,11 @@ SIGNATURES = {
     "origin_sparse_where_above": [vp, vp, vp, vp, i64, i32, C.c_double, vp, i64, vp, vp, vp,
                                   PP(i64)],
     "origin_sparse_zmax_map": [vp, vp, vp, vp, i64, i32, vp, i64, vp],
+    "origin_lines_estimate": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32,
+                              i32, i32, i32, vp, vp, vp, vp, vp, vp, PP(i32)],
+    "origin_lines_gather": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp],
+    "origin_lines_select": [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32,
+                            vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
 _RESTYPE = {"origin_last_error": C.c_char_p}
 

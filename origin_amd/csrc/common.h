@@ -34,6 +34,11 @@ enum OriginKernelId {
   K_LOCAL_MAX,
   K_SMALL,
   K_PCA_TOTAL,  // the whole greedy PCA as one scope (level 1; its kernels are level-2 scopes)
+  K_LINES_GATHER,   // line estimation (lines.hip): gather / standardise / centre, and the clean pass
+  K_LINES_UVEC,     // u = A v / |A v| and the DCT denoising of u
+  K_LINES_PROJECT,  // t = A^T u (column reduction over z)
+  K_LINES_LS,       // residual + weighted least-squares deconvolution, one wave per row
+  K_LINES_SELECT,   // peakdet / flux / mse per grid offset and the winner of each detection
   K_COUNT
 };
 

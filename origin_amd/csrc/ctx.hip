@@ -206,7 +206,8 @@ static const char *kKernelNames[K_COUNT] = {
     "pca_select",      "pca_bmean",          "pca_gather",      "pca_project",   "pca_gram",
     "pca_eig",         "pca_uvec",
     "pca_deflate_dot", "pca_deflate_finish", "pca_flush", "glr_spatial",     "glr_spectral",  "glr_border", "glr_tables",
-    "local_max",       "small",              "pca_total"};
+    "local_max",       "small",              "pca_total",
+    "lines_gather",    "lines_uvec",         "lines_project",   "lines_ls",      "lines_select"};
 
 extern "C" {
 

@@ -336,3 +336,105 @@ def count_above(ctx, cube, thresholds, keep=None):
     _capi.call("origin_count_above", ctx.handle, cube.p, _p(keep), Nz, Ny * Nx, thr.size,
                thr.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
     return out
+
+
+# ------------------------------------------------------------------------- line estimation
+def _lines_tables(raw, psf, weights):
+    """(nfields, P, psf float64 [nf][Nz][P][P], weights float64 [nf][Ny][Nx] or None)."""
+    Nz, Ny, Nx = raw.shape
+    if weights is None:
+        psf = np.asarray(psf, dtype=np.float64)[None]
+        w = None
+    else:
+        psf = np.stack([np.asarray(p, dtype=np.float64) for p in psf])
+        w = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float64) for x in weights]))
+        if w.shape != (psf.shape[0], Ny, Nx):
+            raise ValueError("need one (Ny, Nx) weight map per PSF")
+    psf = np.ascontiguousarray(psf)
+    if psf.ndim != 4 or psf.shape[1] != Nz or psf.shape[2] != psf.shape[3]:
+        raise ValueError(f"PSF must be (Nz, P, P) per field, got {psf.shape[1:]}")
+    return psf.shape[0], psf.shape[2], psf, w
+
+
+def _hp(a):
+    return NULL if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def lines_problem_counts(y0, x0, size_grid, Ny, Nx):
+    """Grid offsets inside the field per detection (lib_origin.py:1703-1706)."""
+    g = int(size_grid)
+    y0, x0 = np.asarray(y0, np.int64), np.asarray(x0, np.int64)
+    ny = np.minimum(y0 + g, Ny - 1) - np.maximum(y0 - g, 0) + 1
+    nx = np.minimum(x0 + g, Nx - 1) - np.maximum(x0 - g, 0) + 1
+    return ny * nx
+
+
+def _lines_outputs(ndet, Nz):
+    return dict(line=np.zeros((ndet, Nz)), var=np.zeros((ndet, Nz)), flux5=np.zeros(ndet),
+                mse5=np.zeros(ndet), yxz=np.zeros((ndet, 3), np.int32),
+                fallback=np.zeros(ndet, np.int32))
+
+
+def _det_rows(z0, y0, x0):
+    return np.ascontiguousarray(np.stack([np.asarray(z0), np.asarray(y0), np.asarray(x0)], axis=1),
+                                dtype=np.int32)
+
+
+def lines_estimate(ctx, raw, var, psf, weights, z0, y0, x0, size_grid=0, criteria=0, order_dct=30,
+                   horiz_psf=1, horiz=5, max_problems=0):
+    """``origin_lines_estimate`` on float32 device cubes: the line estimation of every detection
+    (reference lib_origin.py:1805-1938).  Returns host arrays: ``line`` / ``var`` float64
+    (ndet, Nz), ``flux5``, ``mse5``, ``yxz`` int32 (ndet, 3), ``fallback`` (ndet) and
+    ``nbatch``.  ``criteria``: 0 flux, 1 mse; ``order_dct`` None = PCA LS only."""
+    Nz, Ny, Nx = raw.shape
+    if raw.dtype != np.float32 or var.dtype != np.float32 or var.shape != raw.shape:
+        raise TypeError("lines_estimate needs float32 device cubes of one shape")
+    nf, P, hpsf, hw = _lines_tables(raw, psf, weights)
+    det = _det_rows(z0, y0, x0)
+    out = _lines_outputs(len(det), Nz)
+    nbatch = C.c_int(0)
+    if len(det):
+        _capi.call("origin_lines_estimate", ctx.handle, raw.p, var.p, Nz, Ny, Nx, nf, P, _hp(hpsf),
+                   _hp(hw), len(det), _hp(det), int(size_grid), int(criteria),
+                   -1 if order_dct is None else int(order_dct), int(horiz_psf), int(horiz),
+                   int(max_problems), _hp(out["line"]), _hp(out["var"]), _hp(out["flux5"]),
+                   _hp(out["mse5"]), _hp(out["yxz"]), _hp(out["fallback"]), C.byref(nbatch))
+    out["nbatch"] = nbatch.value
+    return out
+
+
+def lines_gather(ctx, raw, var, psf, weights, centres):
+    """``origin_lines_gather`` (unit-test entry point): the standardised, centred work matrices
+    of the windows centred at ``centres`` ((y, x) rows) -> (A (n, Nz, ld), means (n, Nz),
+    flags (n)) as host arrays."""
+    Nz, Ny, Nx = raw.shape
+    nf, P, hpsf, hw = _lines_tables(raw, psf, weights)
+    cen = np.ascontiguousarray(centres, dtype=np.int32).reshape(-1, 2)
+    n, ld = len(cen), (P * P + 15) // 16 * 16
+    A = ctx.empty((n, Nz, ld), np.float64)
+    mean = ctx.empty((n, Nz), np.float64)
+    flag = ctx.empty((n,), np.int32)
+    _capi.call("origin_lines_gather", ctx.handle, raw.p, var.p, Nz, Ny, Nx, nf, P, _hp(hpsf),
+               _hp(hw), n, _hp(cen), A.p, mean.p, flag.p)
+    return A.to_host(), mean.to_host(), flag.to_host()
+
+
+def lines_select(ctx, raw, psf, weights, z0, y0, x0, deconv, varest, flags, size_grid=0,
+                 criteria=0, horiz_psf=1, horiz=5):
+    """``origin_lines_select`` (unit-test entry point): the grid analysis on given per-problem
+    deconvolutions (rows: per detection its grid offsets inside the field, dy major)."""
+    Nz, Ny, Nx = raw.shape
+    nf, P, hpsf, hw = _lines_tables(raw, psf, weights)
+    det = _det_rows(z0, y0, x0)
+    nprob = int(lines_problem_counts(y0, x0, size_grid, Ny, Nx).sum())
+    dec = np.ascontiguousarray(deconv, dtype=np.float64)
+    ve = np.ascontiguousarray(varest, dtype=np.float64)
+    fl = np.ascontiguousarray(flags, dtype=np.int32)
+    if dec.shape != (nprob, Nz) or ve.shape != (nprob, Nz) or fl.shape != (nprob,):
+        raise ValueError(f"need {nprob} problems of {Nz} channels")
+    out = _lines_outputs(len(det), Nz)
+    _capi.call("origin_lines_select", ctx.handle, raw.p, Nz, Ny, Nx, nf, P, _hp(hpsf), _hp(hw),
+               len(det), _hp(det), int(size_grid), int(criteria), int(horiz_psf), int(horiz),
+               _hp(dec), _hp(ve), _hp(fl), _hp(out["line"]), _hp(out["var"]), _hp(out["flux5"]),
+               _hp(out["mse5"]), _hp(out["yxz"]), _hp(out["fallback"]))
+    return out

@@ -30,6 +30,7 @@ __all__ = (
     'compute_local_max',
     'compute_thresh_gaussfit',
     'Compute_threshold_purity',
+    'estimation_line',
 )
 
 
@@ -217,3 +218,29 @@ def Compute_threshold_purity(purity, cube_local_max, cube_local_min, segmap=None
         return float(threshold), res.as_table()
     except ImportError:
         return float(threshold), res
+
+
+def estimation_line(Cat1, raw, var, psf, wght, wcs, wave, size_grid=1, criteria='flux',
+                    order_dct=30, horiz_psf=1, horiz=5):
+    """Cat2, lin_est, var_est (reference lib_origin.py:1805-1938) through ``lines.estimate_lines``.
+    ``Cat1``: any table-like with ``x0``, ``y0``, ``z0`` columns (an astropy Table, a dict of
+    columns); ``Cat2`` is a dict of NumPy columns in the reference's column order.  ``wcs`` /
+    ``wave`` are used only if not None: ``ra``, ``dec`` and ``lbda`` are then set from the new
+    positions (:1922-1925).  Deviations from the reference: see ``origin_amd.lines``."""
+    from . import lines
+    lines.check_arguments(wght, size_grid, criteria)
+    ctx = _ctx()
+    names = Cat1.colnames if hasattr(Cat1, 'colnames') else list(Cat1.keys())
+    cat = {k: np.asarray(Cat1[k]) for k in names}
+    raw = np.asarray(getattr(raw, '_data', raw))
+    var = np.asarray(getattr(var, '_data', var))
+    d_raw = ctx.to_device(raw, np.float32)
+    d_var = ctx.to_device(np.broadcast_to(var, raw.shape), np.float32)
+    cat2, lin_est, var_est = lines.estimate_lines(ctx, cat, d_raw, d_var, psf, wght, size_grid,
+                                                  criteria, order_dct, horiz_psf, horiz)
+    if wcs is not None:
+        dec, ra = wcs.pix2sky(np.stack((cat2['y'], cat2['x'])).T).T
+        cat2['ra'], cat2['dec'] = ra, dec
+    if wave is not None:
+        cat2['lbda'] = wave.coord(cat2['z'])
+    return cat2, lin_est, var_est
