@@ -502,6 +502,25 @@ int origin_lines_select(origin_ctx *ctx, const float *d_raw, int Nz, int Ny, int
                         double *h_line, double *h_var, double *h_flux5, double *h_mse5, int *h_yxz,
                         int *h_status);
 
+/* ---- F. spatio-spectral merging ------------------------------------------------------
+ * spatiospectral_merging with itersrc (lib_origin.py:1259-1387, called by Detection.run,
+ * steps.py:1014) for n detections given as host arrays in table order.
+ *   h_x, h_y, h_z  int32 [n] inside the (Nz, Ny, Nx) cube; h_area int32 [n] segmap labels;
+ *   h_near, h_far  uint8 [R][R] over (|dx|, |dy|), R <= 64: np.hypot(dx, dy) < tol_spat and
+ *                  np.hypot(dx, dy) > tol_spat * np.sqrt(2) as NumPy evaluates them; outside the
+ *                  tables nothing is near and everything is far.  h_near[0] must be set;
+ *   dzmax          ceil(tol_spec) - 1: |dz| < tol_spec is |dz| <= dzmax;
+ *   h_comp         (may be NULL) lowest row of the row's connected component of the near graph;
+ *   h_area_out     the largest area label of the row's group; h_imatch2 / h_imatch the 0-based
+ *                  group id before / after the spectral stage; all int32 [n] in input row order
+ *                  (the reference returns its table sorted by imatch).
+ * No floating point on the device; results are the same from run to run.  n = 0 is valid.
+ * Synchronises. */
+int origin_merge_detections(origin_ctx *ctx, long n, const int *h_x, const int *h_y,
+                            const int *h_z, const int *h_area, int Ny, int Nx, int Nz, int R,
+                            const uint8_t *h_near, const uint8_t *h_far, int dzmax, int *h_comp,
+                            int *h_area_out, int *h_imatch2, int *h_imatch);
+
 #ifdef __cplusplus
 }
 #endif

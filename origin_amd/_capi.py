@@ -109,6 +109,8 @@ SIGNATURES = {
     "origin_lines_gather": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp],
     "origin_lines_select": [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32,
                             vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "origin_merge_detections": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp,
+                                vp, vp],
 }
 _RESTYPE = {"origin_last_error": C.c_char_p}
 

@@ -39,6 +39,11 @@ enum OriginKernelId {
   K_LINES_PROJECT,  // t = A^T u (column reduction over z)
   K_LINES_LS,       // residual + weighted least-squares deconvolution, one wave per row
   K_LINES_SELECT,   // peakdet / flux / mse per grid offset and the winner of each detection
+  K_MERGE_BIN,       // spatio-spectral merging (merge.hip): rows binned by spaxel
+  K_MERGE_COMP,      // components of the near graph (hook / compress rounds, labels)
+  K_MERGE_STAGE1,    // seeds and their groups, one workgroup per component
+  K_MERGE_RENUMBER,  // seed ranks, group ids, the largest area of a group
+  K_MERGE_STAGE2,    // z bitmaps and the cu / otg walk, one wave per area label
   K_COUNT
 };
 

@@ -438,3 +438,40 @@ def lines_select(ctx, raw, psf, weights, z0, y0, x0, deconv, varest, flags, size
                _hp(dec), _hp(ve), _hp(fl), _hp(out["line"]), _hp(out["var"]), _hp(out["flux5"]),
                _hp(out["mse5"]), _hp(out["yxz"]), _hp(out["fallback"]))
     return out
+
+
+# ------------------------------------------------------------------------- spatio-spectral merging
+def merge_predicate_tables(tol_spat):
+    """The two float predicates of ``itersrc`` (reference lib_origin.py:1300, :1306) over integer
+    offsets, evaluated by NumPy exactly as the reference writes them: ``near[a, b] =
+    np.hypot(a, b) < tol_spat`` and ``far[a, b] = np.hypot(a, b) > tol_spat * np.sqrt(2)`` for
+    ``0 <= a, b <= ceil(tol_spat * sqrt(2)) + 1``.  Beyond the tables nothing is near and
+    everything is far.  (``np.hypot(3, 3)`` and ``3 * np.sqrt(2)`` differ in the last bit: the
+    device never evaluates either.)"""
+    R = int(np.ceil(tol_spat * np.sqrt(2))) + 2
+    a = np.arange(R)
+    d = np.hypot(a[:, None], a[None, :])
+    near = (d < tol_spat).astype(np.uint8)
+    far = (d > tol_spat * np.sqrt(2)).astype(np.uint8)
+    return np.ascontiguousarray(near), np.ascontiguousarray(far)
+
+
+def merge_detections(ctx, x0, y0, z0, area, shape, tol_spat, tol_spec):
+    """``origin_merge_detections``: ``spatiospectral_merging`` (reference lib_origin.py:1319-1387)
+    for detections given as host columns in table order; ``shape`` = (Nz, Ny, Nx) of the cube.
+    Returns int32 host arrays in input row order: ``comp`` (lowest row of the row's connected
+    component of the near graph), ``area`` (the group's largest label), ``imatch2`` and
+    ``imatch`` (0-based group id before / after the spectral stage)."""
+    x, y, z, a = (np.ascontiguousarray(v, dtype=np.int32) for v in (x0, y0, z0, area))
+    n = len(x)
+    if not (len(y) == len(z) == len(a) == n):
+        raise ValueError("x0, y0, z0 and area must have one length")
+    if not tol_spat > 0:
+        raise ValueError("tol_spat must be positive")
+    Nz, Ny, Nx = (int(v) for v in shape)
+    near, far = merge_predicate_tables(tol_spat)
+    out = {k: np.zeros(n, np.int32) for k in ("comp", "area", "imatch2", "imatch")}
+    _capi.call("origin_merge_detections", ctx.handle, n, _hp(x), _hp(y), _hp(z), _hp(a), Ny, Nx,
+               Nz, near.shape[0], _hp(near), _hp(far), int(np.ceil(tol_spec)) - 1, _hp(out["comp"]),
+               _hp(out["area"]), _hp(out["imatch2"]), _hp(out["imatch"]))
+    return out

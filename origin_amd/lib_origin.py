@@ -244,3 +244,30 @@ def estimation_line(Cat1, raw, var, psf, wght, wcs, wave, size_grid=1, criteria=
     if wave is not None:
         cat2['lbda'] = wave.coord(cat2['z'])
     return cat2, lin_est, var_est
+
+
+def _columns(tbl):
+    names = tbl.colnames if hasattr(tbl, 'colnames') else list(tbl.keys())
+    return {k: np.asarray(tbl[k]) for k in names}
+
+
+# The two functions below keep the reference's signatures but return dicts of NumPy columns, as
+# estimation_line does.  They are not in __all__: Detection.run goes on with astropy Table
+# methods on what spatiospectral_merging returns, so swapping them into muse_origin.steps
+# would break it; detection.make_cat1 is the device version of that whole block.
+def spatiospectral_merging(tbl, tol_spat, tol_spec):
+    """The reference's table (lib_origin.py:1319-1387: the input columns, ``area`` replaced,
+    ``imatch``, ``imatch2``, rows sorted by ``imatch``) through ``detection.merge_detections``.
+    ``tbl``: any table-like with ``x0``, ``y0``, ``z0``, ``area`` (an astropy Table, a dict of
+    columns).  Rows of one ``imatch`` come in input order."""
+    from . import detection
+    return detection.merge_detections(_ctx(), _columns(tbl), tol_spat, tol_spec)
+
+
+def purity_estimation(cat, Pval, Pval_comp):
+    """``cat`` (``comp``, ``T_GLR``, ``STD``) as a dict of columns with the ``purity`` column of
+    the reference (lib_origin.py:1941-1991) added.  Host arithmetic (scipy ``interp1d``)."""
+    from . import detection
+    out = _columns(cat)
+    out['purity'] = detection.purity_estimation(out, Pval, Pval_comp)
+    return out
