@@ -115,6 +115,23 @@ int origin_where_above(origin_ctx *ctx, const float *d_cube, const uint8_t *d_au
                        int Nx, double thr, long cap, int *d_z, int *d_y, int *d_x, float *d_val,
                        uint8_t *d_auxout, long *h_count);
 
+/* ---- cube statistics (step 9) ----------------------------------------------------------
+ * add_tglr_stat opens with np.std(correl) and np.std(std) over the two full host cubes
+ * (lib_origin.py:2127-2129, called by CleanResults.run, steps.py:1155-1160).  One streaming pass
+ * over a float32 device cube:
+ *     h_out = (n, sum(x - shift), sum((x - shift)^2))   over the voxels whose spaxel is kept
+ * d_keep: uint8 [S] or NULL, 0 = spaxel excluded (origin_count_above's contract).  Every voxel is
+ * widened to float64 before the subtraction; all sums are float64, in a fixed order (no
+ * floating-point atomics: the same input gives the same bits on every call).  np.std is two calls:
+ * shift = 0 gives the mean, shift = mean gives M2 (origin_amd/kernels.py: cube_std).  d_cube needs
+ * float alignment only, S no particular divisor.  Non-finite input propagates as in NumPy.
+ * Synchronises the stream. */
+int origin_cube_moments(origin_ctx *ctx, const float *d_cube, const uint8_t *d_keep, int Nz, long S,
+                        double shift, double *h_out /* [3] */);
+/* blocks origin_cube_moments launches for a cube of n_voxels (256 lanes x 4 voxels each per
+ * sweep of the grid): a function of the voxel count alone */
+int origin_cube_moments_blocks(long n_voxels);
+
 /* ---- FITS data units ------------------------------------------------
  * Step.dump / Step.load (steps.py:301-352) write and reload every cube / image of a step as a
  * FITS image extension through mpdaf (Cube.write(convert_float32=False) -> float64; lazy

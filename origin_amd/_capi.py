@@ -44,6 +44,8 @@ SIGNATURES = {
     "origin_zmax_map": [vp, vp, vp, i32, i64, vp],
     "origin_count_above": [vp, vp, vp, i32, i64, i32, vp, vp],
     "origin_where_above": [vp, vp, vp, i32, i32, i32, C.c_double, i64, vp, vp, vp, vp, vp, vp],
+    "origin_cube_moments": [vp, vp, vp, i32, i64, C.c_double, vp],
+    "origin_cube_moments_blocks": [i64],
     "origin_fits_encode": [vp, vp, i32, i64, i32, vp],
     "origin_fits_decode": [vp, vp, i32, i64, i32, vp],
     "origin_fits_write_data": [vp, vp, i32, i64, i32, i32],

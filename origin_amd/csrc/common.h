@@ -44,6 +44,7 @@ enum OriginKernelId {
   K_MERGE_STAGE1,    // seeds and their groups, one workgroup per component
   K_MERGE_RENUMBER,  // seed ranks, group ids, the largest area of a group
   K_MERGE_STAGE2,    // z bitmaps and the cu / otg walk, one wave per area label
+  K_STATS,           // moments of a cube (stats.hip): the streaming pass and its final wave
   K_COUNT
 };
 

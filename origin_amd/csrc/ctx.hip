@@ -208,7 +208,8 @@ static const char *kKernelNames[K_COUNT] = {
     "pca_deflate_dot", "pca_deflate_finish", "pca_flush", "glr_spatial",     "glr_spectral",  "glr_border", "glr_tables",
     "local_max",       "small",              "pca_total",
     "lines_gather",    "lines_uvec",         "lines_project",   "lines_ls",      "lines_select",
-    "merge_bin",       "merge_components",   "merge_stage1",    "merge_renumber", "merge_stage2"};
+    "merge_bin",       "merge_components",   "merge_stage1",    "merge_renumber", "merge_stage2",
+    "cube_moments"};
 
 extern "C" {
 

@@ -335,19 +335,33 @@ class FitsCube:
 
 
 # ------------------------------------------------------------------------------- tables
-def write_table(path, columns):
-    """Binary-table extension with float64 ('D') / int64 ('K') columns from a mapping
-    name -> 1-D array (the purity tables of step 6, steps.py:853-854, a few dozen rows: host
-    work).  Layout as astropy's ``Table.write(format='fits')``: empty primary + BINTABLE."""
+_TABLE_STRUCTURE = ("XTENSION", "BITPIX", "NAXIS", "NAXIS1", "NAXIS2", "PCOUNT", "GCOUNT", "TFIELDS")
+
+
+def write_table(path, columns, header=None):
+    """Binary-table extension with float64 ('D'), int64 ('K'), bool ('L': one byte, ``T`` /
+    ``F``) and fixed-width string ('wA': ASCII, blank padded) columns from a mapping name -> 1-D
+    array (the purity tables of step 6, steps.py:853-854, the catalogues of steps 7-9: a few
+    dozen to a few thousand rows, host work).  ``header``: a mapping of further cards of the
+    extension (``CAT3_TS`` of the step-9 tables).  Layout as astropy's
+    ``Table.write(format='fits')``: empty primary + BINTABLE."""
     names = list(columns)
     cols = [np.asarray(columns[k]) for k in names]
     nrows = len(cols[0]) if cols else 0
     fields = []
-    for c in cols:
+    for i, c in enumerate(cols):
         if c.ndim != 1 or len(c) != nrows:
             raise ValueError("table columns must be 1-D and of equal length")
-        fields.append((">i8", "K") if np.issubdtype(c.dtype, np.integer) or c.dtype == bool
-                      else (">f8", "D"))
+        if c.dtype == bool:
+            cols[i] = np.where(c, b"T", b"F").astype("S1")
+            fields.append(("S1", "L"))
+        elif c.dtype.kind in "US":
+            cols[i] = c = np.char.encode(c, "ascii") if c.dtype.kind == "U" else c
+            w = max(c.dtype.itemsize, 1)
+            cols[i] = np.array([s.ljust(w) for s in c.tolist()], dtype=f"S{w}")
+            fields.append((f"S{w}", f"{w}A"))
+        else:
+            fields.append((">i8", "K") if np.issubdtype(c.dtype, np.integer) else (">f8", "D"))
     rec = np.zeros(nrows, dtype=[(n, f[0]) for n, f in zip(names, fields)])
     for n, c in zip(names, cols):
         rec[n] = c
@@ -356,6 +370,10 @@ def write_table(path, columns):
              card("PCOUNT", 0), card("GCOUNT", 1), card("TFIELDS", len(names))]
     for i, (n, f) in enumerate(zip(names, fields)):
         cards += [card(f"TTYPE{i + 1}", n), card(f"TFORM{i + 1}", f[1])]
+    for k, v in (header or {}).items():
+        if k.upper() in _TABLE_STRUCTURE or k.upper().startswith(("TTYPE", "TFORM")):
+            raise ValueError(f"{k} is a structural keyword of the table")
+        cards.append(card(k, v))
     raw = rec.tobytes()
     tmp = path + ".part"
     with open(tmp, "wb") as f:
@@ -366,21 +384,40 @@ def write_table(path, columns):
     return path
 
 
-def read_table(path):
-    """OrderedDict name -> array of the first BINTABLE extension ('D', 'K', 'J', 'E' columns)."""
+def read_table(path, header=None):
+    """OrderedDict name -> array of the first BINTABLE extension: 'D', 'K', 'J', 'E' columns as
+    native numbers, 'L' as bool, 'wA' as ``str`` without the padding.  ``header``: a mapping that
+    receives the extension's cards other than those describing the table's structure."""
     for hdr, off, nb in scan(path):
         if hdr.get("XTENSION") == "BINTABLE":
             break
     else:
         raise KeyError(f"no binary table in {path}")
-    form = {"D": ">f8", "K": ">i8", "J": ">i4", "E": ">f4", "L": "u1"}
-    dt = []
+    form = {"D": ">f8", "K": ">i8", "J": ">i4", "E": ">f4", "L": "S1"}
+    dt, kind = [], {}
     for i in range(1, hdr["TFIELDS"] + 1):
-        tform = str(hdr[f"TFORM{i}"]).strip().lstrip("1")
+        name, tform = str(hdr[f"TTYPE{i}"]), str(hdr[f"TFORM{i}"]).strip()
+        if tform.endswith("A") and (tform[:-1].isdigit() or tform == "A"):
+            dt.append((name, "S%d" % int(tform[:-1] or 1)))
+            kind[name] = "A"
+            continue
+        tform = tform.lstrip("1")
         if tform not in form:
             raise ValueError(f"unsupported column format {hdr[f'TFORM{i}']!r}")
-        dt.append((str(hdr[f"TTYPE{i}"]), form[tform]))
+        dt.append((name, form[tform]))
+        kind[name] = tform
     with open(path, "rb") as f:
         f.seek(off)
         rec = np.frombuffer(f.read(hdr["NAXIS1"] * hdr["NAXIS2"]), dtype=dt)
-    return OrderedDict((n, rec[n].astype(rec[n].dtype.newbyteorder("="))) for n, _ in dt)
+    if header is not None:
+        for k, v in hdr.items():
+            if k not in _TABLE_STRUCTURE and not k.startswith(("TTYPE", "TFORM")):
+                header[k] = v
+
+    def column(n):
+        if kind[n] == "L":
+            return rec[n] == b"T"
+        if kind[n] == "A":
+            return np.char.rstrip(np.char.decode(rec[n], "ascii"))
+        return rec[n].astype(rec[n].dtype.newbyteorder("="))
+    return OrderedDict((n, column(n)) for n, _ in dt)

@@ -338,6 +338,49 @@ def count_above(ctx, cube, thresholds, keep=None):
     return out
 
 
+# ------------------------------------------------------------------------- cube statistics
+MOMENTS_LANES = 256   # lanes per block and voxels per load of origin_cube_moments (csrc/stats.hip)
+MOMENTS_VEC = 4
+
+
+def cube_moments_sweep(n_voxels):
+    """Voxels one sweep of ``origin_cube_moments``'s grid covers for a cube of ``n_voxels``."""
+    return (_capi.load().origin_cube_moments_blocks(int(n_voxels)) * MOMENTS_LANES * MOMENTS_VEC)
+
+
+def cube_moments(ctx, cube, shift=0.0, keep=None):
+    """``(n, sum(x - shift), sum((x - shift)**2))`` as host floats over the voxels of a float32
+    device cube whose spaxel is kept (``keep``: uint8 DeviceArray [Ny*Nx], 0 = excluded, or
+    None): float64 arithmetic in a fixed order, one streaming read, three scalars out."""
+    if cube.dtype != np.float32:
+        raise TypeError("cube_moments needs a float32 device cube")
+    Nz = cube.shape[0]
+    S = cube.size // Nz
+    if keep is not None and (keep.dtype != np.uint8 or keep.size != S):
+        raise ValueError("keep must be a uint8 device array with one entry per spaxel")
+    out = np.zeros(3, dtype=np.float64)
+    _capi.call("origin_cube_moments", ctx.handle, cube.p, _p(keep), Nz, S, float(shift),
+               out.ctypes.data_as(C.c_void_p))
+    return float(out[0]), float(out[1]), float(out[2])
+
+
+def std_from_moments(n, m2):
+    """sqrt(M2 / n) (ddof 0); NaN for n == 0, as ``np.std`` of an empty array."""
+    return float(np.sqrt(m2 / n)) if n > 0 else float("nan")
+
+
+def cube_std(ctx, cube, keep=None):
+    """``np.std(cube)`` of a float32 device cube (over the kept spaxels) in NumPy's own two-pass
+    form (lib_origin.py:2127-2129): the first pass gives the mean, the second the sum of squared
+    deviations from it.  Not ``sum x^2 - (sum x)^2 / n``: that loses the digits a cube with a
+    mean far from 0 needs."""
+    n, s1, _ = cube_moments(ctx, cube, 0.0, keep)
+    if n == 0:
+        return float("nan")
+    _, _, m2 = cube_moments(ctx, cube, s1 / n, keep)
+    return std_from_moments(n, m2)
+
+
 # ------------------------------------------------------------------------- line estimation
 def _lines_tables(raw, psf, weights):
     """(nfields, P, psf float64 [nf][Nz][P][P], weights float64 [nf][Ny][Nx] or None)."""

@@ -271,3 +271,43 @@ def purity_estimation(cat, Pval, Pval_comp):
     out = _columns(cat)
     out['purity'] = detection.purity_estimation(out, Pval, Pval_comp)
     return out
+
+
+# Step 9 (CleanResults.run, steps.py:1149-1160).  Like the two above these return dicts of NumPy
+# columns and are not in __all__: the reference's run body goes on with ``table.meta`` and
+# astropy methods.  ``origin_amd.catalog`` documents the deviations.
+def merge_similar_lines(table, *, z_pix_threshold=5):
+    """The reference's table (lib_origin.py:2140-2222: the input rows sorted by ``(ID, z)`` with
+    ``line_merged_flag`` and ``merged_in`` added) through ``catalog.merge_similar_lines``."""
+    from . import catalog
+    return catalog.merge_similar_lines(_columns(table), z_pix_threshold=z_pix_threshold)
+
+
+def unique_sources(table):
+    """One row per ``ID`` (lib_origin.py:1994-2091) through ``catalog.unique_sources``."""
+    from . import catalog
+    return catalog.unique_sources(_columns(table))
+
+
+def add_tglr_stat(src_table, lines_table, correl, std):
+    """``add_tglr_stat`` (lib_origin.py:2094-2137): ``lines_table`` gains ``nsigTGLR`` and
+    ``nsigSTD`` in place, the returned source table the per-``ID`` maxima.  ``correl`` / ``std``
+    may be host arrays (uploaded as float32), float32 ``DeviceArray`` s, ``LazyCube`` s or cubes
+    tiled over several devices: their standard deviations are reductions on the device
+    (``kernels.cube_std``), only the two scalars come back."""
+    from . import catalog
+    from .device import DeviceArray
+    ctx = _ctx()
+
+    def sigma(c):
+        if isinstance(c, DeviceArray):
+            return kernels.cube_std(ctx, c)
+        if not isinstance(c, np.ndarray):
+            if hasattr(c, 'std'):                                    # session.TiledCube
+                return c.std()
+            if hasattr(c, 'device'):                                 # LazyCube, FitsCube
+                return kernels.cube_std(ctx, c.device(ctx, np.float32))
+        return kernels.cube_std(ctx, ctx.to_device(np.asarray(getattr(c, '_data', c)),
+                                                   np.float32))
+
+    return catalog.add_tglr_stat(_columns(src_table), lines_table, sigma(correl), sigma(std))

@@ -286,6 +286,30 @@ class TiledCube:
             return kernels.count_above(ctx, a, thresholds, k)
         return np.sum(self.group.run(one), axis=0)
 
+    def moments(self, shift=0.0):
+        """``(n, sum(x - shift), sum((x - shift)**2))`` over the whole field
+        (kernels.cube_moments): each rank reduces its own part under the map of the spaxels it
+        owns, the host adds the triples in rank order."""
+        def one(rank):
+            ctx = self.group.ctxs[rank]
+            k = ctx.to_device(self._keep(rank, None).reshape(-1))
+            a = self.parts[rank][0]
+            if hasattr(a, "entries"):
+                a = a.dense()
+            return kernels.cube_moments(ctx, a, shift, k)
+        n = s1 = s2 = 0.0
+        for t in self.group.run(one):
+            n, s1, s2 = n + t[0], s1 + t[1], s2 + t[2]
+        return n, s1, s2
+
+    def std(self):
+        """``np.std`` of the stitched cube, two passes like ``kernels.cube_std``: the global mean
+        of the first pass is the shift of the second on every rank."""
+        n, s1, _ = self.moments(0.0)
+        if n == 0:
+            return float("nan")
+        return kernels.std_from_moments(n, self.moments(s1 / n)[2])
+
     def where_above(self, threshold, aux=None):
         """``np.where(cube > threshold)`` of the stitched cube, in NumPy's order, with the values
         (and those of the uint8 TiledCube ``aux`` with the same parts layout)."""

@@ -13,6 +13,11 @@ Two ways to use them:
   parameter recording, runtime) mirrors reference steps.py:101-352 so tests and the
   benchmark drive the same code without mpdaf.
 
+Steps 7-9 -- ``Detection`` (:895), ``ComputeSpectra`` (:1048), ``CleanResults`` (:1121) -- are here
+as stand-alone classes over ``detection.py``, ``lines.py`` and ``catalog.py``; ``register()``
+leaves the reference's own classes of those steps alone (they work on astropy tables and mpdaf
+objects: INTEGRATION.md).
+
 Cubes produced by one step stay in HBM for the next one (``LazyCube``); a host float64
 copy is only made when somebody reads ``._data``.
 """
@@ -33,6 +38,7 @@ from .device import DeviceArray, default_context
 from .thresholds import compute_thresh_gaussfit
 
 __all__ = ('Preprocessing', 'CreateAreas', 'ComputePCAThreshold', 'ComputeGreedyPCA', 'ComputeTGLR',
+           'ComputePurityThreshold', 'Detection', 'ComputeSpectra', 'CleanResults', 'Catalog',
            'Status', 'Step', 'DataObj', 'SimpleOrig', 'STEPS', 'register', 'unregister')
 
 
@@ -95,12 +101,48 @@ class Status(Enum):
 
 _DONE = (Status.RUN, Status.DUMPED)
 
+class Catalog(OrderedDict):
+    """A table as a dict of NumPy columns that carries header cards in ``meta`` (``CAT3_TS`` of
+    the step-9 tables, reference lib_origin.py:2220, :2089), written to and read from the table
+    extension's header by ``Step.dump`` / ``Step.load``."""
+
+    def __init__(self, columns=(), meta=None):
+        super().__init__(columns)
+        self.meta = OrderedDict(meta or {})
+
+
+def _read_catalog(path):
+    meta = OrderedDict()
+    return Catalog(fitsio.read_table(path, header=meta), meta)
+
+
+def write_spectra(path, spectra):
+    """The ``spectra`` of step 8 (``OrderedDict num_line -> (data, var, z_min)``) as one ``.npz``:
+    ``num_line`` and ``z_min`` (int64, one entry per spectrum, in the dict's order) and, per
+    spectrum, ``data_<num_line>`` and ``var_<num_line>`` (float64)."""
+    doc = dict(num_line=np.array(list(spectra), dtype=np.int64),
+               z_min=np.array([v[2] for v in spectra.values()], dtype=np.int64))
+    for k, (data, var, _) in spectra.items():
+        doc[f'data_{int(k)}'] = np.asarray(data, dtype=np.float64)
+        doc[f'var_{int(k)}'] = np.asarray(var, dtype=np.float64)
+    with open(path, 'wb') as f:
+        np.savez(f, **doc)
+
+
+def read_spectra(path):
+    with np.load(path) as doc:
+        return OrderedDict((int(k), (doc[f'data_{int(k)}'], doc[f'var_{int(k)}'], int(z)))
+                           for k, z in zip(doc['num_line'], doc['z_min']))
+
+
 _READERS = {
     'cube': lambda path: fitsio.FitsCube(path),
     'image': lambda path: fitsio.FitsCube(path),
-    'table': lambda path: fitsio.read_table(path),
+    'table': _read_catalog,
     'array': lambda path: np.loadtxt(path, ndmin=1),
+    'spectra': read_spectra,
 }
+_EXTENSIONS = {'array': 'txt', 'spectra': 'npz'}     # every other kind: 'fits'
 
 
 class DataObj:
@@ -150,6 +192,7 @@ class Step:
     name = None
     desc = None
     require = None
+    on_demand = False     # True: a SimpleOrig makes the step at its first use, not at construction
     _dataobjs = []
 
     def __init_subclass__(cls, **kw):
@@ -212,7 +255,8 @@ class Step:
     def dump(self, outpath):
         """Save the outputs of a step that has been run and replace them by the paths of
         their files (reference steps.py:301-340): ``<outpath>/<name>.fits`` for cubes, images
-        and tables, ``<name>.txt`` for arrays.  Cubes go from HBM to the file through the
+        and tables (``meta`` of a ``Catalog`` as header cards), ``<name>.txt`` for arrays,
+        ``<name>.npz`` for the spectra of step 8 (``write_spectra``).  Cubes go from HBM to the file through the
         device-side FITS encoder (fitsio.write_image), float64 on disk unless the reference
         itself holds another type (``convert_float32=False``, steps.py:319)."""
         if self.status is not Status.RUN:
@@ -222,8 +266,7 @@ class Step:
             obj = getattr(self, name)
             if obj is None:
                 continue
-            ext = 'txt' if kind == 'array' else 'fits'
-            outf = f'{outpath}/{name}.{ext}'
+            outf = f'{outpath}/{name}.{_EXTENSIONS.get(kind, "fits")}'
             self.logger.debug('   - %s [%s]', name, kind)
             if kind in ('cube', 'image'):
                 fitsio.write_image(outf, obj, ctx=ctx, header=self._wcs_cards(kind))
@@ -232,9 +275,12 @@ class Step:
                     obj.write(outf, overwrite=True)
                 else:
                     fitsio.write_table(outf, OrderedDict(
-                        (c, obj[c]) for c in getattr(obj, 'colnames', obj)))
+                        (c, obj[c]) for c in getattr(obj, 'colnames', obj)),
+                        header=getattr(obj, 'meta', None))
             elif kind == 'array':
                 np.savetxt(outf, obj)
+            elif kind == 'spectra':
+                write_spectra(outf, obj)
             # the attribute becomes the path of its file: the data (and its copy in HBM) is
             # released and comes back from the file when the attribute is read again
             setattr(self, name, outf)
@@ -247,8 +293,7 @@ class Step:
         if self.status is not Status.DUMPED:
             return
         for name, kind in self._dataobjs:
-            ext = 'txt' if kind == 'array' else 'fits'
-            setattr(self, name, f'{outpath}/{name}.{ext}')
+            setattr(self, name, f'{outpath}/{name}.{_EXTENSIONS.get(kind, "fits")}')
 
     def _wcs_cards(self, kind):
         """World-coordinate cards of the session (``orig.wcs_header`` / ``orig.wave_header``:
@@ -557,6 +602,120 @@ class _ComputePurityThresholdRun(_HipStepMixin):
         self._loginfo('Threshold: %.2f ', threshold_std)
 
 
+class _DetectionRun(_HipStepMixin):
+    """Detection.run (reference steps.py:941-1045) through ``origin_amd.detection``: the three
+    ``np.where`` scans are stream compactions of the cubes in HBM, the spatio-spectral merging
+    runs on the device (csrc/merge.hip).  ``segmap=None`` uses ``segmap_cont`` as it is: the
+    reference's extra ``phot_deblend_sources`` pass over it (:1006) needs photutils and stays
+    with the caller, who hands its result in as ``segmap``."""
+    name = 'detection'
+    desc = 'Thresholding and spatio-spectral merging'
+
+    def det_correl_min(self, thresh=None):
+        """3D positions of detections in correl_min (steps.py:935-939)."""
+        from . import detection
+        orig = self.orig
+        thresh = thresh or orig.param['threshold']
+        ctx = _ctx_of(orig)
+        return detection.det_correl_min(ctx, self._get_cube(orig, ctx, 'cube_local_min'), thresh)
+
+    def run(self, orig, threshold=None, threshold_std=None, tol_spat=3, tol_spec=5,
+            maxdist_lines=2.5, segmap=None):
+        from . import detection
+        if threshold is not None:
+            orig.threshold_correl = threshold
+        if threshold_std is not None:
+            orig.threshold_std = threshold_std
+        self._loginfo('Thresholding correl (>%.2f) and std (>%.2f)', orig.threshold_correl,
+                      orig.threshold_std)
+        cat0, cat, cat_std = detection.from_session(orig, maxdist_lines=maxdist_lines)
+        self._loginfo('%d detected lines', len(cat['z0']))
+        self._loginfo('%d detected lines', len(cat0['z0']) - len(cat['z0']))
+        self.Cat0 = cat0
+        self._loginfo('kept %d lines from std after filtering', len(cat_std['z0']))
+
+        if segmap is not None:
+            self.logger.info('Overriding segmap_cont with the given one')
+            seg = _data(segmap)
+            if seg.shape != tuple(orig.shape[1:]):
+                raise ValueError('segmap does not have the same shape as the processed cube')
+        else:
+            self.logger.info('Using segmap_cont as it is: the deblending step is the caller\'s '
+                             '(pass its result as segmap)')
+            seg = _data(orig.segmap_cont)
+        self.store_image('segmap_label', seg)
+
+        self.logger.info('Spatio-spectral merging...')
+        self._loginfo('Purity estimation')
+        cat1 = detection.make_cat1(_ctx_of(orig), cat, cat_std, seg, orig.Pval, orig.Pval_comp,
+                                   tol_spat, tol_spec, getattr(orig, 'wcs', None),
+                                   getattr(orig, 'wave', None))
+        comp = cat1['comp'] == 1
+        ns = len(set(cat1['ID']))
+        ds = len(set(cat1['ID'][comp]) - set(cat1['ID']))
+        self.Cat1 = cat1
+        msg = 'Save the catalog in self.Cat1 (%d [+%s] sources, %d [+%d] lines)'
+        self._loginfo(msg, ns, ds, len(comp), int(np.count_nonzero(comp)))
+
+
+class _ComputeSpectraRun(_HipStepMixin):
+    """ComputeSpectra.run (reference steps.py:1082-1118) through ``origin_amd.lines``.
+    ``spectra`` is an ``OrderedDict num_line -> (data, var, z_min)``: the estimated line and its
+    variance on the channels ``z_min .. z_min + len(data) - 1``, that is ``z - r .. z + r`` clipped
+    to the cube with ``r = ceil(FWHM_profiles[profile] * spectrum_size_fwhm / 2)`` (:1104-1116;
+    the reference wraps the same window in an mpdaf ``Spectrum``).  Without
+    ``orig.FWHM_profiles`` the lines are kept whole (``z_min`` 0).  Fallback rows
+    (``len(data) == 1``) have no spectrum, as at :1112."""
+    name = 'compute_spectra'
+    desc = 'Lines estimation'
+    require = ('detection',)
+
+    def run(self, orig, grid_dxy=0, spectrum_size_fwhm=6):
+        from . import lines
+        cat2, line_est, line_var = lines.from_session(orig, orig.Cat1, grid_dxy)
+        self.Cat2 = cat2
+        self._loginfo('Save the updated catalog in self.Cat2 (%d lines)', len(cat2['z']))
+
+        fwhm = getattr(orig, 'FWHM_profiles', None)
+        radius = None
+        if fwhm is not None:   # radius for spectrum trimming
+            radius = np.ceil(np.array(fwhm) * spectrum_size_fwhm / 2).astype(int)
+        spectra = OrderedDict()
+        for profile, z, num_line, data, vari in zip(cat2['profile'], cat2['z'], cat2['num_line'],
+                                                    line_est, line_var):
+            if len(data) <= 1:
+                continue
+            z_min, z_max = 0, len(data)
+            if radius is not None:
+                z_min = max(int(z) - int(radius[profile]), 0)
+                z_max = min(int(z) + int(radius[profile]) + 1, len(data))
+            spectra[int(num_line)] = (data[z_min:z_max], vari[z_min:z_max], z_min)
+        self.spectra = spectra
+        self._loginfo('Save estimated spectrum of each line in self.spectra')
+
+
+class _CleanResultsRun(_HipStepMixin):
+    """CleanResults.run (reference steps.py:1149-1171) through ``origin_amd.catalog``: the table
+    work on the host, the two cube standard deviations of ``add_tglr_stat`` as reductions of the
+    cubes in HBM (csrc/stats.hip)."""
+    name = 'clean_results'
+    desc = 'Results cleaning'
+    require = ('compute_spectra',)
+
+    def run(self, orig, merge_lines_z_threshold=5):
+        from . import catalog
+        lines_, src, ts = catalog.from_session(
+            orig, merge_lines_z_threshold=merge_lines_z_threshold)
+        self.Cat3_lines = Catalog(lines_, {'CAT3_TS': ts})
+        self.Cat3_sources = Catalog(src, {'CAT3_TS': ts})
+        self._loginfo('Save the unique source catalog in self.Cat3_sources (%d sources)',
+                      len(src['ID']))
+        self._loginfo('Save the cleaned lines in self.Cat3_lines (%d lines)', len(lines_['ID']))
+        nb_line_merged = int(np.sum(lines_['merged_in'] != catalog.NOT_MERGED))
+        if nb_line_merged:
+            self._loginfo('%d lines were merged in nearby lines', nb_line_merged)
+
+
 def _data(img):
     """ndarray of an image attribute (mpdaf Image under the reference, ndarray here)."""
     return np.asarray(getattr(img, '_data', img))
@@ -631,19 +790,59 @@ class ComputePurityThreshold(_ComputePurityThresholdRun, Step):
     segmap_purity = DataObj('image')
 
 
+class Detection(_DetectionRun, Step):
+    __doc__ = _DetectionRun.__doc__
+    on_demand = True
+    Cat0 = DataObj('table')
+    Cat1 = DataObj('table')
+    segmap_label = DataObj('image')
+
+
+class ComputeSpectra(_ComputeSpectraRun, Step):
+    __doc__ = _ComputeSpectraRun.__doc__
+    on_demand = True
+    Cat2 = DataObj('table')
+    spectra = DataObj('spectra')
+
+
+class CleanResults(_CleanResultsRun, Step):
+    __doc__ = _CleanResultsRun.__doc__
+    on_demand = True
+    Cat3_lines = DataObj('table')
+    Cat3_sources = DataObj('table')
+
+
+# (steps 10 and 11 of the reference -- CreateMasks, SaveSources -- are not here: DESIGN.md 7)
 STEPS = [Preprocessing, CreateAreas, ComputePCAThreshold, ComputeGreedyPCA, ComputeTGLR,
-         ComputePurityThreshold]
+         ComputePurityThreshold, Detection, ComputeSpectra, CleanResults]
+
+
+class _SessionSteps(OrderedDict):
+    """The steps of a session by name, in ``STEPS`` order; looking up an ``on_demand`` step that
+    has not been used yet makes it."""
+
+    def __init__(self, make):
+        super().__init__()
+        self._make = make
+
+    def __missing__(self, name):
+        return self._make(name)
 
 
 class SimpleOrig:
     """Stand-in for the ``ORIGIN`` session object carrying exactly what the four hot ``run``
     bodies read: cube_raw, var, mask, FWHM_PSF, PSF, wfields, profiles,
     nbAreas, areamap, param, testO2, thresO2, cube_std, cube_faint.  Steps are bound as
-    ``stepNN_name`` callables like origin.py:193-208 does."""
+    ``stepNN_name`` callables like origin.py:193-208 does.  Steps 1-6 are made with the session;
+    steps 7-9 (``Step.on_demand``) when their method, one of their outputs or ``steps[name]`` is
+    first used, so a session that stops at step 6 lists, dumps and records in ``param`` what it
+    always did."""
 
     def __init__(self, cube_raw, var, mask, PSF, profiles, FWHM_PSF=3.3, wfields=None,
-                 param=None, ctx=None, devices=None, backend=None):
-        """``devices``: None (one context, ``ctx`` or device 0) or a list of device ordinals --
+                 param=None, ctx=None, devices=None, backend=None, FWHM_profiles=None):
+        """``FWHM_profiles``: FWHM of every profile of the dictionary in channels (origin.py:168),
+        the window of the spectra step 8 keeps; None keeps the lines whole.
+        ``devices``: None (one context, ``ctx`` or device 0) or a list of device ordinals --
         the hot steps then run tiled over them in this one process (origin_amd/session.py); the
         same ordinal twice = two contexts on one card.  ``backend``: "rccl" / "host" for the
         cubes that travel between them (default: RCCL when the ordinals differ)."""
@@ -652,20 +851,41 @@ class SimpleOrig:
         self.cube_raw, self.var, self.mask = cube_raw, var, mask
         self.PSF, self.wfields, self.profiles = PSF, wfields, profiles
         self.FWHM_PSF = FWHM_PSF
+        self.FWHM_profiles = FWHM_profiles
         self.param = param or {}
         self.wave = self.wcs = None
         self.testO2 = self.histO2 = self.binO2 = None
         self.hip_ctx = ctx or default_context(0 if not devices else int(devices[0]))
-        self.steps = OrderedDict()
+        self.steps = _SessionSteps(self._make_step)
         self._dataobjs = {}
+        self._on_demand = {}       # name -> (idx, class) of the steps not made yet
         for i, cls in enumerate(STEPS, start=1):
-            step = cls(self, i, self.param)
-            self.steps[step.name] = step
-            self.__dict__[step.method_name] = step
-            for name, _ in step._dataobjs:
-                self._dataobjs[name] = step
+            if cls.on_demand:
+                self._on_demand[cls.name] = (i, cls)
+            else:
+                self._bind(i, cls)
+
+    def _bind(self, idx, cls):
+        step = cls(self, idx, self.param)
+        self.steps[step.name] = step
+        for name in sorted(self.steps, key=lambda n: self.steps[n].idx):   # keep the STEPS order
+            self.steps.move_to_end(name)
+        self.__dict__[step.method_name] = step
+        for name, _ in step._dataobjs:
+            self._dataobjs[name] = step
+        return step
+
+    def _make_step(self, name):
+        """An ``on_demand`` step at its first use (KeyError for a name that is no step)."""
+        idx, cls = self.__dict__.get('_on_demand', {}).pop(name)
+        return self._bind(idx, cls)
 
     def __getattr__(self, name):
+        # the method or an output of a step that has not been made yet makes it
+        for sname, (idx, cls) in list(self.__dict__.get('_on_demand', {}).items()):
+            if name == f'step{idx:02d}_{sname}' or any(name == n for n, _ in cls._dataobjs):
+                self._make_step(sname)
+                return getattr(self, name)
         d = self.__dict__.get('_dataobjs', {})
         if name in d:
             return getattr(d[name], name)
@@ -674,6 +894,30 @@ class SimpleOrig:
     @property
     def nbAreas(self):
         return self.param.get('nbareas')
+
+    @property
+    def shape(self):
+        """(Nz, Ny, Nx) of the processed cube."""
+        return tuple(getattr(self.cube_raw, '_data', self.cube_raw).shape)
+
+    # the thresholds of step 6, overridden by step 7's keywords (origin.py:496-513)
+    @property
+    def threshold_correl(self):
+        """Estimated threshold used to detect lines on local maxima of max correl."""
+        return self.param.get('threshold')
+
+    @threshold_correl.setter
+    def threshold_correl(self, value):
+        self.param['threshold'] = value
+
+    @property
+    def threshold_std(self):
+        """Estimated threshold used to detect complementary lines on local maxima of std cube."""
+        return self.param.get('threshold_std')
+
+    @threshold_std.setter
+    def threshold_std(self, value):
+        self.param['threshold_std'] = value
 
 
 # ----------------------------------------------------------------------------- register
