@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -169,6 +170,47 @@ int origin_spatial_mfma_launch(origin_ctx *ctx, int terms, const float *A, const
                                const float *taps, int Nz, int Ny, int Nx, int P, int accf,
                                float *out, int ry0 = 0, int nry = 0, int rx0 = 0, int nrx = 0);
 long origin_spatial_mfma_count(int terms, int Nz, int Ny, int Nx, int P);
+
+// An origin_malloc'd block that is freed with its scope, and the host drivers' way to lay a
+// workspace out in one (merge.hip, lines.hip): the pieces are listed once, in a layout function.
+struct DevMem {
+  origin_ctx *ctx;
+  void *p = nullptr;
+  explicit DevMem(origin_ctx *c) : ctx(c) {}
+  int alloc(size_t bytes) { return origin_malloc(ctx, std::max(bytes, (size_t)256), &p); }
+  ~DevMem() {
+    if (p) (void)origin_free(ctx, p);
+  }
+};
+
+struct Carver {  // consecutive 256-byte aligned pieces of one block; null base: sizes only
+  size_t off = 0;
+  char *base = nullptr;
+  template <class T>
+  T *take(size_t n) {
+    T *r = base ? (T *)(base + off) : nullptr;
+    off += (n * sizeof(T) + 255) & ~(size_t)255;
+    return r;
+  }
+};
+
+// `layout(Carver &)` takes its pieces and stores their pointers: once without a block, for the
+// size; then `mem` is allocated and the layout runs again on it.  The allocation's ORIGIN_* code.
+template <class Layout>
+int carve_block(origin_ctx *ctx, DevMem &mem, Layout &&layout) {
+  Carver c;
+  layout(c);
+  const int rc = mem.alloc(c.off);
+  if (rc) return rc;
+  c.off = 0, c.base = (char *)mem.p;
+  layout(c);
+  return ORIGIN_OK;
+}
+
+template <class T>
+int put(origin_ctx *ctx, T *d, const std::vector<T> &h) {
+  return origin_h2d(ctx, d, h.data(), h.size() * sizeof(T));
+}
 
 #define ORIGIN_CHECK_ARG(cond, ...)       \
   do {                                    \

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.h"
+#include "pca_eig.h"
 
 namespace {
 
@@ -386,35 +387,6 @@ __global__ __launch_bounds__(64) void select_kernel(Field f, const int *__restri
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct DevMem {  // origin_malloc'd block, freed with the scope
-  origin_ctx *ctx;
-  void *p = nullptr;
-  explicit DevMem(origin_ctx *c) : ctx(c) {}
-  int alloc(size_t bytes) { return origin_malloc(ctx, std::max(bytes, (size_t)256), &p); }
-  ~DevMem() {
-    if (p) (void)origin_free(ctx, p);
-  }
-};
-
-struct Carver {  // consecutive 256-byte aligned pieces of one block
-  size_t off = 0;
-  char *base = nullptr;
-  template <class T>
-  T *take(size_t n) {
-    T *r = base ? (T *)(base + off) : nullptr;
-    off += (n * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-  }
-};
-
-// the K-split gram_launch (pca.hip) picks for a tile list of `ntiles`
-int gram_ksplit(int num_cu, long ntiles, int Nz) {
-  long ks = ((long)num_cu * 8 + ntiles - 1) / ntiles;
-  ks = std::max(1l, std::min(32l, ks));
-  if (ks > Nz / 64) ks = Nz / 64 > 0 ? Nz / 64 : 1;
-  return (int)ks;
-}
-
 struct Problems {
   std::vector<int> cen;  // (cy, cx) per problem
   std::vector<int> det;  // (z0, y0, x0, first problem, problems) per detection
@@ -492,9 +464,7 @@ struct Work {
   long *xp_off, *g_off, *ld, *n, *q_off, *v_off, *gx_off, *gg_off;
   int *ti, *tj, *ta, *cen, *det, *flag, *o_yxz, *o_status;
   int nslab, gmax, tpp;
-  size_t carve(char *base, const Field &f, long nb, long nd) {
-    Carver c;
-    c.base = base;
+  void layout(Carver &c, const Field &f, long nb, long nd) {
     const long Nz = f.Nz, ld = f.ld;
     A = c.take<double>(nb * Nz * ld), mean = c.take<double>(nb * Nz);
     G = c.take<double>(nb * ld * ld), v = c.take<double>(nb * ld), u = c.take<double>(nb * Nz);
@@ -509,14 +479,8 @@ struct Work {
     ta = c.take<int>((long)gmax * tpp);
     cen = c.take<int>(2 * nb), det = c.take<int>(5 * nd), flag = c.take<int>(nb);
     o_yxz = c.take<int>(3 * nd), o_status = c.take<int>(nd);
-    return c.off;
   }
 };
-
-template <class T>
-int put(origin_ctx *ctx, T *d, const std::vector<T> &h) {
-  return origin_h2d(ctx, d, h.data(), h.size() * sizeof(T));
-}
 
 // Gram product, leading eigenvector and u = A v / |A v| of the nb matrices in W.A.  The Gram
 // launches cover groups of at most W.gmax problems: every group size up to gmax gives gram_launch
@@ -569,26 +533,122 @@ int run_gather(origin_ctx *ctx, const Field &f, int nb, const int *cen, double *
   return ORIGIN_OK;
 }
 
-int run_select(origin_ctx *ctx, const Field &f, Work &W, int nd, int use_mse, int hp, int horiz) {
+// what the batches of a call share: how a detection's winner is picked, the DCT denoising of u
+// (DCTMAT(Nz, K - 1) on the device, K == 0: none) and the caller's arrays, one row per detection
+struct Call {
+  int criteria, horiz_psf, horiz, K;
+  const double *dct;
+  double *line, *var, *flux, *mse;
+  int *yxz, *status;
+};
+
+int run_select(origin_ctx *ctx, const Field &f, Work &W, int nd, const Call &c) {
   ProfScope ps(ctx, K_LINES_SELECT);
   hipLaunchKernelGGL(select_kernel, dim3(nd), dim3(64), 0, ctx->stream, f, W.det, W.cen, W.flag,
-                     W.dec, W.varest, use_mse, hp, horiz, W.o_line, W.o_var, W.o_flux, W.o_mse,
-                     W.o_yxz, W.o_status);
+                     W.dec, W.varest, c.criteria, c.horiz_psf, c.horiz, W.o_line, W.o_var, W.o_flux,
+                     W.o_mse, W.o_yxz, W.o_status);
   ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }
 
 // results of nd detections, starting at detection d0 of the caller's arrays
-int fetch_results(origin_ctx *ctx, const Field &f, Work &W, int d0, int nd, double *h_line,
-                  double *h_var, double *h_flux, double *h_mse, int *h_yxz, int *h_status) {
+int fetch_results(origin_ctx *ctx, const Field &f, Work &W, int d0, int nd, const Call &h) {
   const size_t lb = (size_t)nd * f.Nz * sizeof(double);
   int rc;
-  if ((rc = origin_d2h(ctx, h_line + (size_t)d0 * f.Nz, W.o_line, lb))) return rc;
-  if ((rc = origin_d2h(ctx, h_var + (size_t)d0 * f.Nz, W.o_var, lb))) return rc;
-  if ((rc = origin_d2h(ctx, h_flux + d0, W.o_flux, nd * sizeof(double)))) return rc;
-  if ((rc = origin_d2h(ctx, h_mse + d0, W.o_mse, nd * sizeof(double)))) return rc;
-  if ((rc = origin_d2h(ctx, h_yxz + 3 * (size_t)d0, W.o_yxz, 3 * nd * sizeof(int)))) return rc;
-  return origin_d2h(ctx, h_status + d0, W.o_status, nd * sizeof(int));
+  if ((rc = origin_d2h(ctx, h.line + (size_t)d0 * f.Nz, W.o_line, lb))) return rc;
+  if ((rc = origin_d2h(ctx, h.var + (size_t)d0 * f.Nz, W.o_var, lb))) return rc;
+  if ((rc = origin_d2h(ctx, h.flux + d0, W.o_flux, nd * sizeof(double)))) return rc;
+  if ((rc = origin_d2h(ctx, h.mse + d0, W.o_mse, nd * sizeof(double)))) return rc;
+  if ((rc = origin_d2h(ctx, h.yxz + 3 * (size_t)d0, W.o_yxz, 3 * nd * sizeof(int)))) return rc;
+  return origin_d2h(ctx, h.status + d0, W.o_status, nd * sizeof(int));
+}
+
+// DCTMAT(Nz, K - 1) (lib :127-147) as [Nz][K] on the device, built once per call; K == 0: none
+int upload_dct(origin_ctx *ctx, int Nz, int K, DevMem &dct) {
+  if (K <= 0) return ORIGIN_OK;
+  std::vector<double> D((size_t)Nz * K);
+  for (int z = 0; z < Nz; ++z)
+    for (int k = 0; k < K; ++k) {
+      const double c = std::sqrt(2.0 / Nz) * std::cos((z + 0.5) * (M_PI / Nz) * k);
+      D[(size_t)z * K + k] = k == 0 ? c * (1.0 / std::sqrt(2.0)) : c;
+    }
+  const int rc = dct.alloc(D.size() * sizeof(double));
+  return rc ? rc : origin_h2d(ctx, dct.p, D.data(), D.size() * sizeof(double));
+}
+
+// the largest Gram group that keeps ks1, a single problem's K-split, within 256 MiB of slabs
+int gram_group(int num_cu, int tpp, int Nz, long ld, int ks1) {
+  int g = 1;
+  while (g < 1024 && pca_gram_ksplit(num_cu, (long)(g + 1) * tpp, Nz) == ks1 &&
+         (size_t)ks1 * (g + 1) * ld * ld * sizeof(double) <= ((size_t)256 << 20))
+    ++g;
+  return g;
+}
+
+// problems per batch (whole detections): from the free memory unless the caller says
+long batch_capacity(size_t free_b, const Field &f, Work &W, int ks1, int size_grid, int max_prob) {
+  const int ncand_max = (2 * size_grid + 1) * (2 * size_grid + 1);
+  Carver one;  // (sizes only: a null base)
+  W.layout(one, f, 1, 1);
+  const size_t per_problem = one.off + (size_t)origin_pca_eig_qrows() * f.ld * 8 +
+                             (size_t)ks1 * f.ld * f.ld * 8;
+  long cap = (long)(free_b / 2 / per_problem);
+  cap = std::max((long)ncand_max, std::min(cap, 8192l));
+  if (max_prob > 0) cap = std::max((long)ncand_max, std::min(cap, (long)max_prob));
+  return cap;
+}
+
+// descriptors of origin_pca_gram (one group, reused by every group) and origin_pca_eig
+int upload_descriptors(origin_ctx *ctx, const Field &f, Work &W, long cap) {
+  const long Nz = f.Nz, ld = f.ld;
+  const int nt = (int)((ld + 31) / 32);
+  std::vector<long> xo(cap), go(cap), lds(cap, ld), ns(cap, f.P2), qo(cap), vo(cap);
+  for (long i = 0; i < cap; ++i) {
+    xo[i] = i * Nz * ld, go[i] = i * ld * ld, vo[i] = i * ld;
+    qo[i] = i * origin_pca_eig_qrows() * ld;
+  }
+  std::vector<int> ti, tj, ta;
+  for (int a = 0; a < W.gmax; ++a)
+    for (int i = 0; i < nt; ++i)
+      for (int j = i; j < nt; ++j) ti.push_back(i), tj.push_back(j), ta.push_back(a);
+  int rc;
+  if ((rc = put(ctx, W.xp_off, xo)) || (rc = put(ctx, W.g_off, go)) || (rc = put(ctx, W.ld, lds)) ||
+      (rc = put(ctx, W.n, ns)) || (rc = put(ctx, W.q_off, qo)) || (rc = put(ctx, W.v_off, vo)) ||
+      (rc = put(ctx, W.ti, ti)) || (rc = put(ctx, W.tj, tj)) || (rc = put(ctx, W.ta, ta)))
+    return rc;
+  xo.resize(W.gmax), go.resize(W.gmax);
+  if ((rc = put(ctx, W.gx_off, xo))) return rc;
+  return put(ctx, W.gg_off, go);
+}
+
+// detections [d0, d1) of the call, nb problems: the header's steps on one batch
+int estimate_batch(origin_ctx *ctx, const Field &f, Work &W, const Problems &pr, int d0, int d1,
+                   int nb, const Call &c) {
+  const int nd = d1 - d0, p0 = pr.det[5 * d0 + 3];
+  std::vector<int> det(pr.det.begin() + 5 * d0, pr.det.begin() + 5 * d1);
+  for (int d = 0; d < nd; ++d) det[5 * d + 3] -= p0;
+  int rc;
+  if ((rc = origin_h2d(ctx, W.cen, pr.cen.data() + 2 * (size_t)p0, 2 * (size_t)nb * sizeof(int))))
+    return rc;
+  if ((rc = put(ctx, W.det, det))) return rc;
+  if ((rc = run_gather(ctx, f, nb, W.cen, W.A, W.mean, W.flag))) return rc;
+  if ((rc = leading_vectors(ctx, f, W, nb))) return rc;
+  if ((rc = project_and_deconvolve<0>(ctx, f, W, nb))) return rc;
+  {
+    ProfScope ps(ctx, K_LINES_GATHER);
+    hipLaunchKernelGGL(gather_kernel<1>, dim3(cdiv(f.Nz, 4), nb), dim3(64, 4), 0, ctx->stream, f,
+                       W.cen, W.dec, W.A, (double *)nullptr, W.flag);
+    ORIGIN_LAUNCH_CHECK();
+  }
+  if ((rc = leading_vectors(ctx, f, W, nb))) return rc;
+  if (c.K > 0) {
+    ProfScope ps(ctx, K_LINES_UVEC);
+    hipLaunchKernelGGL(dct_kernel, dim3(nb), dim3(256), 0, ctx->stream, f.Nz, c.K, c.dct, W.u);
+    ORIGIN_LAUNCH_CHECK();
+  }
+  if ((rc = project_and_deconvolve<1>(ctx, f, W, nb))) return rc;
+  if ((rc = run_select(ctx, f, W, nd, c))) return rc;
+  return fetch_results(ctx, f, W, d0, nd, c);
 }
 
 }  // namespace
@@ -633,29 +693,24 @@ int origin_lines_select(origin_ctx *ctx, const float *d_raw, int Nz, int Ny, int
   list_problems(h_det, ndet, size_grid, Ny, Nx, pr);
   const int nb = (int)(pr.cen.size() / 2);
   Work W = {};
-  W.nslab = 0, W.gmax = 0, W.tpp = 0;
-  // only the pieces the selection touches
-  Carver c;
   DevMem mem(ctx);
-  for (int pass = 0; pass < 2; ++pass) {
-    c.off = 0;
+  rc = carve_block(ctx, mem, [&](Carver &c) {  // only the pieces the selection touches
     W.dec = c.take<double>((long)nb * Nz), W.varest = c.take<double>((long)nb * Nz);
     W.o_line = c.take<double>((long)ndet * Nz), W.o_var = c.take<double>((long)ndet * Nz);
     W.o_flux = c.take<double>(ndet), W.o_mse = c.take<double>(ndet);
     W.cen = c.take<int>(2 * nb), W.det = c.take<int>(5 * ndet), W.flag = c.take<int>(nb);
     W.o_yxz = c.take<int>(3 * ndet), W.o_status = c.take<int>(ndet);
-    if (pass == 0) {
-      if ((rc = mem.alloc(c.off))) return rc;
-      c.base = (char *)mem.p;
-    }
-  }
+  });
+  if (rc) return rc;
   const size_t db = (size_t)nb * Nz * sizeof(double);
   if ((rc = origin_h2d(ctx, W.dec, h_deconv, db))) return rc;
   if ((rc = origin_h2d(ctx, W.varest, h_varest, db))) return rc;
   if ((rc = origin_h2d(ctx, W.flag, h_flag, (size_t)nb * sizeof(int)))) return rc;
   if ((rc = put(ctx, W.cen, pr.cen)) || (rc = put(ctx, W.det, pr.det))) return rc;
-  if ((rc = run_select(ctx, f, W, ndet, criteria, horiz_psf, horiz))) return rc;
-  return fetch_results(ctx, f, W, 0, ndet, h_line, h_var, h_flux5, h_mse5, h_yxz, h_status);
+  const Call call = {criteria, horiz_psf, horiz, 0, nullptr,  // (no DCT in the selection)
+                     h_line, h_var, h_flux5, h_mse5, h_yxz, h_status};
+  if ((rc = run_select(ctx, f, W, ndet, call))) return rc;
+  return fetch_results(ctx, f, W, 0, ndet, call);
 }
 
 int origin_lines_estimate(origin_ctx *ctx, const float *d_raw, const float *d_var, int Nz, int Ny,
@@ -677,101 +732,34 @@ int origin_lines_estimate(origin_ctx *ctx, const float *d_raw, const float *d_va
   Field f = make_field(d_raw, d_var, Nz, Ny, Nx, nfields, P);
   Tables tab(ctx);
   if ((rc = tab.upload(ctx, f, h_psf, h_weights))) return rc;
-  // DCTMAT(Nz, order_dct) (lib :127-147), built once per call
-  const int K = order_dct + 1;
   DevMem dct(ctx);
-  if (K > 0) {
-    std::vector<double> D((size_t)Nz * K);
-    for (int z = 0; z < Nz; ++z)
-      for (int k = 0; k < K; ++k) {
-        const double c = std::sqrt(2.0 / Nz) * std::cos((z + 0.5) * (M_PI / Nz) * k);
-        D[(size_t)z * K + k] = k == 0 ? c * (1.0 / std::sqrt(2.0)) : c;
-      }
-    if ((rc = dct.alloc(D.size() * sizeof(double)))) return rc;
-    if ((rc = origin_h2d(ctx, dct.p, D.data(), D.size() * sizeof(double)))) return rc;
-  }
-
+  if ((rc = upload_dct(ctx, Nz, order_dct + 1, dct))) return rc;
   Problems pr;
   list_problems(h_det, ndet, size_grid, Ny, Nx, pr);
-  const int ncand_max = (2 * size_grid + 1) * (2 * size_grid + 1);
-  const long ld = f.ld;
-  const int nt = (int)((ld + 31) / 32);
+  const int nt = (f.ld + 31) / 32;
   Work W = {};
   W.nslab = cdiv(Nz, LN_SLAB);
   W.tpp = nt * (nt + 1) / 2;
-  // the largest Gram group that keeps a single problem's K-split, within 256 MiB of slabs
-  const int ks1 = gram_ksplit(ctx->num_cu, W.tpp, Nz);
-  W.gmax = 1;
-  while (W.gmax < 1024 && gram_ksplit(ctx->num_cu, (long)(W.gmax + 1) * W.tpp, Nz) == ks1 &&
-         (size_t)ks1 * (W.gmax + 1) * ld * ld * sizeof(double) <= ((size_t)256 << 20))
-    ++W.gmax;
-
-  // problems per batch: whole detections, from the free memory unless the caller says
+  const int ks1 = pca_gram_ksplit(ctx->num_cu, W.tpp, Nz);
+  W.gmax = gram_group(ctx->num_cu, W.tpp, Nz, f.ld, ks1);
   size_t free_b = 0, total_b = 0;
   if ((rc = origin_mem_info(ctx, &free_b, &total_b))) return rc;
-  const size_t per_problem = W.carve(nullptr, f, 1, 1) + (size_t)origin_pca_eig_qrows() * ld * 8 +
-                             (size_t)ks1 * ld * ld * 8;
-  long cap = (long)(free_b / 2 / per_problem);
-  cap = std::max((long)ncand_max, std::min(cap, 8192l));
-  if (max_problems > 0) cap = std::max((long)ncand_max, std::min(cap, (long)max_problems));
+  const long cap = batch_capacity(free_b, f, W, ks1, size_grid, max_problems);
   W.gmax = (int)std::min((long)W.gmax, cap);
   DevMem mem(ctx);
   const long nd_cap = std::min((long)ndet, cap);
-  if ((rc = mem.alloc(W.carve(nullptr, f, cap, nd_cap)))) return rc;
-  W.carve((char *)mem.p, f, cap, nd_cap);
+  if ((rc = carve_block(ctx, mem, [&](Carver &c) { W.layout(c, f, cap, nd_cap); }))) return rc;
+  if ((rc = upload_descriptors(ctx, f, W, cap))) return rc;
 
-  // descriptors of origin_pca_gram (one group, reused by every group) and origin_pca_eig
-  {
-    std::vector<long> xo(cap), go(cap), lds(cap, ld), ns(cap, f.P2), qo(cap), vo(cap);
-    for (long i = 0; i < cap; ++i) {
-      xo[i] = i * Nz * ld, go[i] = i * ld * ld, vo[i] = i * ld;
-      qo[i] = i * origin_pca_eig_qrows() * ld;
-    }
-    std::vector<int> ti, tj, ta;
-    for (int a = 0; a < W.gmax; ++a)
-      for (int i = 0; i < nt; ++i)
-        for (int j = i; j < nt; ++j) ti.push_back(i), tj.push_back(j), ta.push_back(a);
-    if ((rc = put(ctx, W.xp_off, xo)) || (rc = put(ctx, W.g_off, go)) || (rc = put(ctx, W.ld, lds)) ||
-        (rc = put(ctx, W.n, ns)) || (rc = put(ctx, W.q_off, qo)) || (rc = put(ctx, W.v_off, vo)) ||
-        (rc = put(ctx, W.ti, ti)) || (rc = put(ctx, W.tj, tj)) || (rc = put(ctx, W.ta, ta)))
-      return rc;
-    xo.resize(W.gmax), go.resize(W.gmax);
-    if ((rc = put(ctx, W.gx_off, xo)) || (rc = put(ctx, W.gg_off, go))) return rc;
-  }
-
+  const Call call = {criteria, horiz_psf, horiz, order_dct + 1, (const double *)dct.p,
+                     h_line, h_var, h_flux5, h_mse5, h_yxz, h_status};
   int nbatch = 0;
-  for (int d0 = 0; d0 < ndet;) {
+  for (int d0 = 0; d0 < ndet; ++nbatch) {
     int d1 = d0;
     long nb = 0;
     while (d1 < ndet && nb + pr.det[5 * d1 + 4] <= cap) nb += pr.det[5 * d1 + 4], ++d1;
-    const int nd = d1 - d0, p0 = pr.det[5 * d0 + 3];
-    std::vector<int> det(pr.det.begin() + 5 * d0, pr.det.begin() + 5 * d1);
-    for (int d = 0; d < nd; ++d) det[5 * d + 3] -= p0;
-    if ((rc = origin_h2d(ctx, W.cen, pr.cen.data() + 2 * (size_t)p0, 2 * nb * sizeof(int)))) return rc;
-    if ((rc = put(ctx, W.det, det))) return rc;
-
-    if ((rc = run_gather(ctx, f, (int)nb, W.cen, W.A, W.mean, W.flag))) return rc;
-    if ((rc = leading_vectors(ctx, f, W, (int)nb))) return rc;
-    if ((rc = project_and_deconvolve<0>(ctx, f, W, (int)nb))) return rc;
-    {
-      ProfScope ps(ctx, K_LINES_GATHER);
-      hipLaunchKernelGGL(gather_kernel<1>, dim3(cdiv(Nz, 4), (int)nb), dim3(64, 4), 0, ctx->stream,
-                         f, W.cen, W.dec, W.A, (double *)nullptr, W.flag);
-      ORIGIN_LAUNCH_CHECK();
-    }
-    if ((rc = leading_vectors(ctx, f, W, (int)nb))) return rc;
-    if (K > 0) {
-      ProfScope ps(ctx, K_LINES_UVEC);
-      hipLaunchKernelGGL(dct_kernel, dim3((int)nb), dim3(256), 0, ctx->stream, Nz, K,
-                         (const double *)dct.p, W.u);
-      ORIGIN_LAUNCH_CHECK();
-    }
-    if ((rc = project_and_deconvolve<1>(ctx, f, W, (int)nb))) return rc;
-    if ((rc = run_select(ctx, f, W, nd, criteria, horiz_psf, horiz))) return rc;
-    if ((rc = fetch_results(ctx, f, W, d0, nd, h_line, h_var, h_flux5, h_mse5, h_yxz, h_status)))
-      return rc;
+    if ((rc = estimate_batch(ctx, f, W, pr, d0, d1, (int)nb, call))) return rc;
     d0 = d1;
-    ++nbatch;
   }
   if (h_nbatch) *h_nbatch = nbatch;
   return ORIGIN_OK;

@@ -312,27 +312,6 @@ __global__ __launch_bounds__(64) void stage2_kernel(const int *aoff, int W, unsi
 }
 
 // ------------------------------------------------------------------------------------ host side
-struct DevMem {  // origin_malloc'd block, freed with the scope
-  origin_ctx *ctx;
-  void *p = nullptr;
-  explicit DevMem(origin_ctx *c) : ctx(c) {}
-  int alloc(size_t bytes) { return origin_malloc(ctx, std::max(bytes, (size_t)256), &p); }
-  ~DevMem() {
-    if (p) (void)origin_free(ctx, p);
-  }
-};
-
-struct Carver {  // consecutive 256-byte aligned pieces of one block
-  size_t off = 0;
-  char *base = nullptr;
-  template <class T>
-  T *take(size_t n) {
-    T *r = base ? (T *)(base + off) : nullptr;
-    off += (n * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-  }
-};
-
 inline int grid_for(long n) { return (int)std::max(1l, std::min((n + MG_BLOCK - 1) / MG_BLOCK, 4096l)); }
 
 #define MG_LAUNCH(kernel, grid, block, lds, ...)                                   \
@@ -340,6 +319,209 @@ inline int grid_for(long n) { return (int)std::max(1l, std::min((n + MG_BLOCK - 
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, ctx->stream, __VA_ARGS__); \
     ORIGIN_LAUNCH_CHECK();                                                         \
   } while (0)
+
+// (host) rows ordered by component (a component's label is its lowest row), largest component
+// first, rows ascending: `members`, and comp_off[0 .. nc] into it
+void order_by_component(const std::vector<int> &comp, std::vector<int> &members,
+                        std::vector<int> &comp_off) {
+  const int N = (int)comp.size();
+  std::vector<int> size(N, 0), order, slot(N);
+  for (int r = 0; r < N; ++r) ++size[comp[r]];
+  for (int r = 0; r < N; ++r)
+    if (size[r]) order.push_back(r);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return size[a] > size[b]; });
+  const int nc = (int)order.size();
+  comp_off.assign(nc + 1, 0);
+  for (int i = 0; i < nc; ++i) slot[order[i]] = i, comp_off[i + 1] = comp_off[i] + size[order[i]];
+  std::vector<int> cur(comp_off.begin(), comp_off.end() - 1);
+  members.resize(N);
+  for (int r = 0; r < N; ++r) members[cur[slot[comp[r]]]++] = r;
+}
+
+// (host) groups per area label > 0, labels ascending; a label with one group is done.  slot_group:
+// the other labels' groups, aoff[0 .. na] into it; gslot: a group's slot or -1.  Returns kmax,
+// the most groups of one label.
+int label_groups(int N, const int *gid, const int *area, std::vector<int> &slot_group,
+                 std::vector<int> &aoff, std::vector<int> &gslot) {
+  int ng = 0;
+  for (int r = 0; r < N; ++r) ng = std::max(ng, gid[r] + 1);
+  std::vector<int> garea_h(ng, 0), glist;
+  for (int r = 0; r < N; ++r) garea_h[gid[r]] = area[r];
+  for (int g = 0; g < ng; ++g)
+    if (garea_h[g] > 0) glist.push_back(g);
+  std::stable_sort(glist.begin(), glist.end(),
+                   [&](int a, int b) { return garea_h[a] < garea_h[b]; });
+  slot_group.clear(), aoff.assign(1, 0), gslot.assign(ng, -1);
+  int kmax = 0;
+  for (size_t i = 0; i < glist.size();) {
+    size_t j = i;
+    while (j < glist.size() && garea_h[glist[j]] == garea_h[glist[i]]) ++j;
+    if (j - i > 1) {
+      for (size_t q = i; q < j; ++q) gslot[glist[q]] = (int)slot_group.size(), slot_group.push_back(glist[q]);
+      aoff.push_back((int)slot_group.size());
+      kmax = std::max(kmax, (int)(j - i));
+    }
+    i = j;
+  }
+  return kmax;
+}
+
+// One call: the sizes, the call's block and stage 2's with their pieces, and one method per stage
+// of the launch sequence in the header.
+struct MergeRun {
+  origin_ctx *ctx;
+  const int N, S, Ny, Nx, Nz, R, wr, dzmax;  // wr: half-width of the near window
+  const size_t nb;                           // bytes of a column
+  const int gn, gs;
+  DevMem mem, mem2;
+  int *x, *y, *z, *area, *key, *binrows, *start, *cursor, *parent, *complow, *comp, *members,
+      *comp_off, *imatch, *queue, *rank, *gid, *garea, *area_out, *flag;
+  uint8_t *near_t, *far_t;
+  int *d_rowslot, *d_aoff, *link, *root;
+  unsigned *B, *D;
+
+  MergeRun(origin_ctx *c, int n, int ny, int nx, int nz, int r, int w, int dz)
+      : ctx(c), N(n), S(ny * nx), Ny(ny), Nx(nx), Nz(nz), R(r), wr(w), dzmax(dz),
+        nb((size_t)n * sizeof(int)), gn(grid_for(n)), gs(grid_for(ny * nx)), mem(c), mem2(c) {}
+
+  int setup(const int *h_x, const int *h_y, const int *h_z, const int *h_area,
+            const uint8_t *h_near, const uint8_t *h_far) {
+    int rc = carve_block(ctx, mem, [&](Carver &c) {
+      x = c.take<int>(N), y = c.take<int>(N), z = c.take<int>(N), area = c.take<int>(N);
+      key = c.take<int>(N), binrows = c.take<int>(N);
+      start = c.take<int>(S + 1), cursor = c.take<int>(S + 1);
+      parent = c.take<int>(S), complow = c.take<int>(S), comp = c.take<int>(N);
+      members = c.take<int>(N), comp_off = c.take<int>(N + 1);
+      imatch = c.take<int>(N), queue = c.take<int>(N), rank = c.take<int>(N + 1);
+      gid = c.take<int>(N), garea = c.take<int>(N), area_out = c.take<int>(N);
+      flag = c.take<int>(1);
+      near_t = c.take<uint8_t>(R * R), far_t = c.take<uint8_t>(R * R);
+    });
+    if (rc) return rc;
+    if ((rc = origin_h2d(ctx, x, h_x, nb)) || (rc = origin_h2d(ctx, y, h_y, nb)) ||
+        (rc = origin_h2d(ctx, z, h_z, nb)) || (rc = origin_h2d(ctx, area, h_area, nb)) ||
+        (rc = origin_h2d(ctx, near_t, h_near, (size_t)R * R)))
+      return rc;
+    return origin_h2d(ctx, far_t, h_far, (size_t)R * R);
+  }
+
+  int bin() {
+    ProfScope ps(ctx, K_MERGE_BIN);
+    ORIGIN_HIP(hipMemsetAsync(start, 0, (size_t)(S + 1) * sizeof(int), ctx->stream));
+    MG_LAUNCH(hist_kernel, gn, MG_BLOCK, 0, N, x, y, Nx, key, start);
+    MG_LAUNCH(scan_kernel, 1, MG_SCAN, 0, S, start);
+    ORIGIN_HIP(hipMemcpyAsync(cursor, start, (size_t)(S + 1) * sizeof(int),
+                              hipMemcpyDeviceToDevice, ctx->stream));
+    MG_LAUNCH(scatter_kernel, gn, MG_BLOCK, 0, N, key, cursor, binrows);
+    return ORIGIN_OK;
+  }
+
+  // components of the near graph; hcomp: the label of every row, a row not above it
+  int components(std::vector<int> &hcomp) {
+    MG_LAUNCH(parent_init_kernel, gs, MG_BLOCK, 0, S, start, parent, complow);
+    int rc, changed = 1;
+    for (long round = 0; changed; ++round) {
+      if (round > (long)N + 1) {  // (every round that changes something removes a root)
+        origin_set_error("component labelling did not converge in %ld rounds", round);
+        return ORIGIN_E_STATE;
+      }
+      {
+        ProfScope ps(ctx, K_MERGE_COMP);
+        ORIGIN_HIP(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
+        MG_LAUNCH(hook_kernel, gs, MG_BLOCK, 0, Ny, Nx, R, wr, near_t, parent, flag);
+        MG_LAUNCH(compress_kernel, gs, MG_BLOCK, 0, S, parent);
+      }
+      if ((rc = origin_d2h(ctx, &changed, flag, sizeof(int)))) return rc;
+    }
+    {
+      ProfScope ps(ctx, K_MERGE_COMP);
+      MG_LAUNCH(complow_kernel, gn, MG_BLOCK, 0, N, key, parent, complow);
+      MG_LAUNCH(comp_kernel, gn, MG_BLOCK, 0, N, key, parent, complow, comp);
+    }
+    hcomp.resize(N);
+    if ((rc = origin_d2h(ctx, hcomp.data(), comp, nb))) return rc;
+    for (int r = 0; r < N; ++r)
+      if (hcomp[r] < 0 || hcomp[r] > r) {
+        origin_set_error("component label %d of row %d is not a lower row", hcomp[r], r);
+        return ORIGIN_E_STATE;
+      }
+    return ORIGIN_OK;
+  }
+
+  int stage1(const std::vector<int> &h_members, const std::vector<int> &h_comp_off) {
+    const int nc = (int)h_comp_off.size() - 1;
+    int rc;
+    if ((rc = put(ctx, members, h_members)) || (rc = put(ctx, comp_off, h_comp_off))) return rc;
+    ProfScope ps(ctx, K_MERGE_STAGE1);
+    ORIGIN_HIP(hipMemsetAsync(imatch, 0xff, nb, ctx->stream));
+    Stage1Args a = {nc, comp_off, members, x, y, z, start, binrows, Ny, Nx, R, wr, dzmax,
+                    near_t, far_t, imatch, queue};
+    MG_LAUNCH(stage1_kernel, std::min(nc, 4 * std::max(ctx->num_cu, 1)), MG_BLOCK, 0, a);
+    return ORIGIN_OK;
+  }
+
+  // rank of the seed among the seeds = group id, the group's largest area
+  int renumber(int *h_gid, int *h_area_out) {
+    {
+      ProfScope ps(ctx, K_MERGE_RENUMBER);
+      ORIGIN_HIP(hipMemsetAsync(gid, 0xff, nb, ctx->stream));
+      MG_LAUNCH(seed_flag_kernel, gn, MG_BLOCK, 0, N, imatch, rank);
+      MG_LAUNCH(scan_kernel, 1, MG_SCAN, 0, N, rank);
+      MG_LAUNCH(group_kernel<0>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
+      MG_LAUNCH(group_kernel<1>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
+      MG_LAUNCH(group_kernel<2>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
+    }
+    int rc;
+    if ((rc = origin_d2h(ctx, h_gid, gid, nb)) || (rc = origin_d2h(ctx, h_area_out, area_out, nb)))
+      return rc;
+    for (int r = 0; r < N; ++r)
+      if (h_gid[r] < 0 || h_gid[r] > r) {
+        origin_set_error("row %d was left without a group", r);
+        return ORIGIN_E_STATE;
+      }
+    return ORIGIN_OK;
+  }
+
+  // the slots' groups that merge; h_imatch: a row's group, replaced by the group's survivor
+  int stage2(const std::vector<int> &slot_group, const std::vector<int> &aoff,
+             const std::vector<int> &gslot, int kmax, const int *h_gid, int *h_imatch) {
+    const int na = (int)aoff.size() - 1, nslots = (int)slot_group.size();
+    const size_t lds = (size_t)((kmax + 31) / 32) * sizeof(unsigned);
+    ORIGIN_CHECK_ARG(lds <= MG_S2_LDS, "an area label holds %d groups (limit %d)", kmax,
+                     MG_S2_LDS * 8);
+    const int W = (Nz + 31) / 32;
+    std::vector<int> rowslot(N), root_h(nslots);
+    for (int r = 0; r < N; ++r) rowslot[r] = gslot[h_gid[r]];
+    int rc = carve_block(ctx, mem2, [&](Carver &c) {
+      d_rowslot = c.take<int>(N), d_aoff = c.take<int>(na + 1);
+      link = c.take<int>(nslots), root = c.take<int>(nslots);
+      B = c.take<unsigned>((size_t)nslots * W), D = c.take<unsigned>((size_t)nslots * W);
+    });
+    if (rc) return rc;
+    if ((rc = put(ctx, d_rowslot, rowslot)) || (rc = put(ctx, d_aoff, aoff))) return rc;
+    {
+      ProfScope ps(ctx, K_MERGE_STAGE2);
+      // (B and D are adjacent pieces of one block)
+      ORIGIN_HIP(hipMemsetAsync(B, 0, (size_t)((char *)D - (char *)B) + (size_t)nslots * W * sizeof(unsigned),
+                                ctx->stream));
+      MG_LAUNCH(bitmap_kernel, gn, MG_BLOCK, 0, N, z, d_rowslot, Nz, W, dzmax, B, D);
+      MG_LAUNCH(stage2_kernel, na, 64, lds, d_aoff, W, B, D, link, root);
+    }
+    if ((rc = origin_d2h(ctx, root_h.data(), root, (size_t)nslots * sizeof(int)))) return rc;
+    std::vector<int> final_gid(nslots);  // a slot's survivor, as a group id
+    for (int a = 0; a < na; ++a)
+      for (int s = aoff[a]; s < aoff[a + 1]; ++s) {
+        if (root_h[s] < 0 || root_h[s] >= aoff[a + 1] - aoff[a]) {
+          origin_set_error("spectral stage: group slot %d has no survivor", s);
+          return ORIGIN_E_STATE;
+        }
+        final_gid[s] = slot_group[aoff[a] + root_h[s]];
+      }
+    for (int r = 0; r < N; ++r)
+      if (rowslot[r] >= 0) h_imatch[r] = final_gid[rowslot[r]];
+    return ORIGIN_OK;
+  }
+};
 
 }  // namespace
 
@@ -368,189 +550,19 @@ int origin_merge_detections(origin_ctx *ctx, long n, const int *h_x, const int *
   for (int a = 0; a < R; ++a)
     for (int b = 0; b < R; ++b)
       if (h_near[a * R + b]) wr = std::max(wr, std::max(a, b));
-  const int N = (int)n, S = Ny * Nx;
-  const size_t nb = (size_t)N * sizeof(int);
+  MergeRun run(ctx, (int)n, Ny, Nx, Nz, R, wr, dzmax);
+  std::vector<int> hcomp, members, comp_off, slot_group, aoff, gslot;
   int rc;
-
-  DevMem mem(ctx);
-  Carver c;
-  int *x, *y, *z, *area, *key, *binrows, *start, *cursor, *parent, *complow, *comp, *members,
-      *comp_off, *imatch, *queue, *rank, *gid, *garea, *area_out, *flag;
-  uint8_t *near_t, *far_t;
-  for (int pass = 0; pass < 2; ++pass) {
-    c.off = 0;
-    x = c.take<int>(N), y = c.take<int>(N), z = c.take<int>(N), area = c.take<int>(N);
-    key = c.take<int>(N), binrows = c.take<int>(N);
-    start = c.take<int>(S + 1), cursor = c.take<int>(S + 1);
-    parent = c.take<int>(S), complow = c.take<int>(S), comp = c.take<int>(N);
-    members = c.take<int>(N), comp_off = c.take<int>(N + 1);
-    imatch = c.take<int>(N), queue = c.take<int>(N), rank = c.take<int>(N + 1);
-    gid = c.take<int>(N), garea = c.take<int>(N), area_out = c.take<int>(N);
-    flag = c.take<int>(1);
-    near_t = c.take<uint8_t>(R * R), far_t = c.take<uint8_t>(R * R);
-    if (pass == 0) {
-      if ((rc = mem.alloc(c.off))) return rc;
-      c.base = (char *)mem.p;
-    }
-  }
-  if ((rc = origin_h2d(ctx, x, h_x, nb)) || (rc = origin_h2d(ctx, y, h_y, nb)) ||
-      (rc = origin_h2d(ctx, z, h_z, nb)) || (rc = origin_h2d(ctx, area, h_area, nb)) ||
-      (rc = origin_h2d(ctx, near_t, h_near, (size_t)R * R)) ||
-      (rc = origin_h2d(ctx, far_t, h_far, (size_t)R * R)))
+  if ((rc = run.setup(h_x, h_y, h_z, h_area, h_near, h_far)) || (rc = run.bin()) ||
+      (rc = run.components(hcomp)))
     return rc;
-  const int gn = grid_for(N), gs = grid_for(S);
-
-  {  // bin
-    ProfScope ps(ctx, K_MERGE_BIN);
-    ORIGIN_HIP(hipMemsetAsync(start, 0, (size_t)(S + 1) * sizeof(int), ctx->stream));
-    MG_LAUNCH(hist_kernel, gn, MG_BLOCK, 0, N, x, y, Nx, key, start);
-    MG_LAUNCH(scan_kernel, 1, MG_SCAN, 0, S, start);
-    ORIGIN_HIP(hipMemcpyAsync(cursor, start, (size_t)(S + 1) * sizeof(int),
-                              hipMemcpyDeviceToDevice, ctx->stream));
-    MG_LAUNCH(scatter_kernel, gn, MG_BLOCK, 0, N, key, cursor, binrows);
-  }
-
-  std::vector<int> hcomp(N);
-  {  // components of the near graph
-    MG_LAUNCH(parent_init_kernel, gs, MG_BLOCK, 0, S, start, parent, complow);
-    int changed = 1;
-    for (long round = 0; changed; ++round) {
-      if (round > n + 1) {  // (every round that changes something removes a root)
-        origin_set_error("component labelling did not converge in %ld rounds", round);
-        return ORIGIN_E_STATE;
-      }
-      {
-        ProfScope ps(ctx, K_MERGE_COMP);
-        ORIGIN_HIP(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
-        MG_LAUNCH(hook_kernel, gs, MG_BLOCK, 0, Ny, Nx, R, wr, near_t, parent, flag);
-        MG_LAUNCH(compress_kernel, gs, MG_BLOCK, 0, S, parent);
-      }
-      if ((rc = origin_d2h(ctx, &changed, flag, sizeof(int)))) return rc;
-    }
-    ProfScope ps(ctx, K_MERGE_COMP);
-    MG_LAUNCH(complow_kernel, gn, MG_BLOCK, 0, N, key, parent, complow);
-    MG_LAUNCH(comp_kernel, gn, MG_BLOCK, 0, N, key, parent, complow, comp);
-  }
-  if ((rc = origin_d2h(ctx, hcomp.data(), comp, nb))) return rc;
-  for (int r = 0; r < N; ++r)
-    if (hcomp[r] < 0 || hcomp[r] > r) {
-      origin_set_error("component label %d of row %d is not a lower row", hcomp[r], r);
-      return ORIGIN_E_STATE;
-    }
-  if (h_comp) memcpy(h_comp, hcomp.data(), nb);
-
-  // rows by component (a component's label is its lowest row), largest component first
-  int nc = 0;
-  {
-    std::vector<int> size(N, 0), order, slot(N), off;
-    for (int r = 0; r < N; ++r) ++size[hcomp[r]];
-    for (int r = 0; r < N; ++r)
-      if (size[r]) order.push_back(r);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return size[a] > size[b]; });
-    nc = (int)order.size();
-    off.resize(nc + 1);
-    off[0] = 0;
-    for (int i = 0; i < nc; ++i) slot[order[i]] = i, off[i + 1] = off[i] + size[order[i]];
-    std::vector<int> cur(off.begin(), off.end() - 1), mem_h(N);
-    for (int r = 0; r < N; ++r) mem_h[cur[slot[hcomp[r]]]++] = r;
-    if ((rc = origin_h2d(ctx, members, mem_h.data(), nb)) ||
-        (rc = origin_h2d(ctx, comp_off, off.data(), (size_t)(nc + 1) * sizeof(int))))
-      return rc;
-  }
-
-  {  // stage 1
-    ProfScope ps(ctx, K_MERGE_STAGE1);
-    ORIGIN_HIP(hipMemsetAsync(imatch, 0xff, nb, ctx->stream));
-    Stage1Args a = {nc, comp_off, members, x, y, z, start, binrows, Ny, Nx, R, wr, dzmax,
-                    near_t, far_t, imatch, queue};
-    MG_LAUNCH(stage1_kernel, std::min(nc, 4 * std::max(ctx->num_cu, 1)), MG_BLOCK, 0, a);
-  }
-  {  // renumber: rank of the seed among the seeds, the group's largest area
-    ProfScope ps(ctx, K_MERGE_RENUMBER);
-    ORIGIN_HIP(hipMemsetAsync(gid, 0xff, nb, ctx->stream));
-    MG_LAUNCH(seed_flag_kernel, gn, MG_BLOCK, 0, N, imatch, rank);
-    MG_LAUNCH(scan_kernel, 1, MG_SCAN, 0, N, rank);
-    MG_LAUNCH(group_kernel<0>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
-    MG_LAUNCH(group_kernel<1>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
-    MG_LAUNCH(group_kernel<2>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
-  }
-  if ((rc = origin_d2h(ctx, h_imatch2, gid, nb)) || (rc = origin_d2h(ctx, h_area_out, area_out, nb)))
-    return rc;
-  for (int r = 0; r < N; ++r)
-    if (h_imatch2[r] < 0 || h_imatch2[r] > r) {
-      origin_set_error("row %d was left without a group", r);
-      return ORIGIN_E_STATE;
-    }
-  memcpy(h_imatch, h_imatch2, nb);
-
-  // stage 2: the groups of every area label > 0, ascending; a label with one group is done
-  int ng = 0;
-  for (int r = 0; r < N; ++r) ng = std::max(ng, h_imatch2[r] + 1);
-  std::vector<int> garea_h(ng, 0), glist;
-  for (int r = 0; r < N; ++r) garea_h[h_imatch2[r]] = h_area_out[r];
-  for (int g = 0; g < ng; ++g)
-    if (garea_h[g] > 0) glist.push_back(g);
-  std::stable_sort(glist.begin(), glist.end(),
-                   [&](int a, int b) { return garea_h[a] < garea_h[b]; });
-  std::vector<int> slot_group, aoff(1, 0), gslot(ng, -1);
-  int kmax = 0;
-  for (size_t i = 0; i < glist.size();) {
-    size_t j = i;
-    while (j < glist.size() && garea_h[glist[j]] == garea_h[glist[i]]) ++j;
-    if (j - i > 1) {
-      for (size_t q = i; q < j; ++q) gslot[glist[q]] = (int)slot_group.size(), slot_group.push_back(glist[q]);
-      aoff.push_back((int)slot_group.size());
-      kmax = std::max(kmax, (int)(j - i));
-    }
-    i = j;
-  }
-  const int na = (int)aoff.size() - 1, nslots = (int)slot_group.size();
-  if (na == 0) return ORIGIN_OK;
-  const size_t lds = (size_t)((kmax + 31) / 32) * sizeof(unsigned);
-  ORIGIN_CHECK_ARG(lds <= MG_S2_LDS, "an area label holds %d groups (limit %d)", kmax,
-                   MG_S2_LDS * 8);
-  const int W = (Nz + 31) / 32;
-  std::vector<int> rowslot(N), root_h(nslots);
-  for (int r = 0; r < N; ++r) rowslot[r] = gslot[h_imatch2[r]];
-  DevMem mem2(ctx);
-  Carver c2;
-  int *d_rowslot, *d_aoff, *link, *root;
-  unsigned *B, *D;
-  for (int pass = 0; pass < 2; ++pass) {
-    c2.off = 0;
-    d_rowslot = c2.take<int>(N), d_aoff = c2.take<int>(na + 1);
-    link = c2.take<int>(nslots), root = c2.take<int>(nslots);
-    B = c2.take<unsigned>((size_t)nslots * W), D = c2.take<unsigned>((size_t)nslots * W);
-    if (pass == 0) {
-      if ((rc = mem2.alloc(c2.off))) return rc;
-      c2.base = (char *)mem2.p;
-    }
-  }
-  if ((rc = origin_h2d(ctx, d_rowslot, rowslot.data(), nb)) ||
-      (rc = origin_h2d(ctx, d_aoff, aoff.data(), (size_t)(na + 1) * sizeof(int))))
-    return rc;
-  {
-    ProfScope ps(ctx, K_MERGE_STAGE2);
-    // (B and D are adjacent pieces of one block)
-    ORIGIN_HIP(hipMemsetAsync(B, 0, (size_t)((char *)D - (char *)B) + (size_t)nslots * W * sizeof(unsigned),
-                              ctx->stream));
-    MG_LAUNCH(bitmap_kernel, gn, MG_BLOCK, 0, N, z, d_rowslot, Nz, W, dzmax, B, D);
-    MG_LAUNCH(stage2_kernel, na, 64, lds, d_aoff, W, B, D, link, root);
-  }
-  if ((rc = origin_d2h(ctx, root_h.data(), root, (size_t)nslots * sizeof(int)))) return rc;
-  // a slot's survivor, as a group id
-  std::vector<int> final_gid(nslots);
-  for (int a = 0; a < na; ++a)
-    for (int s = aoff[a]; s < aoff[a + 1]; ++s) {
-      if (root_h[s] < 0 || root_h[s] >= aoff[a + 1] - aoff[a]) {
-        origin_set_error("spectral stage: group slot %d has no survivor", s);
-        return ORIGIN_E_STATE;
-      }
-      final_gid[s] = slot_group[aoff[a] + root_h[s]];
-    }
-  for (int r = 0; r < N; ++r)
-    if (rowslot[r] >= 0) h_imatch[r] = final_gid[rowslot[r]];
-  return ORIGIN_OK;
+  if (h_comp) memcpy(h_comp, hcomp.data(), run.nb);
+  order_by_component(hcomp, members, comp_off);
+  if ((rc = run.stage1(members, comp_off)) || (rc = run.renumber(h_imatch2, h_area_out))) return rc;
+  memcpy(h_imatch, h_imatch2, run.nb);
+  const int kmax = label_groups(run.N, h_imatch2, h_area_out, slot_group, aoff, gslot);
+  if (aoff.size() == 1) return ORIGIN_OK;  // every label has one group
+  return run.stage2(slot_group, aoff, gslot, kmax, h_imatch2, h_imatch);
 }
 
 }  // extern "C"

@@ -1221,11 +1221,7 @@ int gram_launch(origin_ctx *ctx, const double *d_Xp, const long *d_xp_off, const
                 double *d_G, const long *d_g_off, bool skip_reduce = false,
                 const double **slab_out = nullptr, int *ksplit_out = nullptr,
                 const long *d_n = nullptr) {
-  // K-split so that small problems still put >= ~8 waves on every CU
-  int ksplit = (int)(((long)ctx->num_cu * 8 + ntiles - 1) / ntiles);
-  if (ksplit < 1) ksplit = 1;
-  if (ksplit > 32) ksplit = 32;
-  if (ksplit > Nz / 64) ksplit = Nz / 64 > 0 ? Nz / 64 : 1;
+  const int ksplit = pca_gram_ksplit(ctx->num_cu, ntiles, Nz);
   void *scr = nullptr;
   int rc = origin_scratch(ctx, (size_t)ksplit * g_total * sizeof(double), &scr);
   if (rc) return rc;

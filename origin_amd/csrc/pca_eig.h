@@ -1,7 +1,19 @@
 // What pca.hip and pca_eig.hip share: the eigen-solver's launch and the sizes its caller lays
-// buffers out by, and the wave reduction both files' kernels use.
+// buffers out by, and the wave reduction both files' kernels use.  And what pca.hip and lines.hip
+// share: the K-split of a Gram launch, which lines.hip sizes its Gram groups by.
 #pragma once
 #include "common.h"
+
+// K-split of a Gram launch over `ntiles` tiles, so that small problems still put >= ~8 waves on
+// every CU.  The one copy of the rule: gram_launch (pca.hip) splits by it, and lines.hip keeps its
+// Gram groups small enough to get the split of a single problem.
+inline int pca_gram_ksplit(int num_cu, long ntiles, int Nz) {
+  int ksplit = (int)(((long)num_cu * 8 + ntiles - 1) / ntiles);
+  if (ksplit < 1) ksplit = 1;
+  if (ksplit > 32) ksplit = 32;
+  if (ksplit > Nz / 64) ksplit = Nz / 64 > 0 ? Nz / 64 : 1;
+  return ksplit;
+}
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 

@@ -11,11 +11,10 @@ single-matrix tests and of the header of test_hip_parity.py:
                 1 - |v . v_lapack| <= 1e-10 / max(gap, 1e-12)^2 + 1e-13, v[n:ld] == 0
   cube_faint  : mapO2 and nstop identical, max-abs <= 1e-4, rel-Frobenius <= 2e-6
 """
-import re
-
 import numpy as np
 import pytest
 
+from _gram_geometry import gram_geometry, num_cu_of
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
@@ -42,21 +41,7 @@ def ld_of(n):
     return (n + 15) // 16 * 16
 
 
-def num_cu_of(ctx):
-    m = re.search(r"(\d+) CUs", ctx.name)
-    return int(m.group(1)) if m else 256
-
-
 # ------------------------------------------------------------------------------- Gram batches
-def gram_geometry(num_cu, ntiles, Nz):
-    """(ksplit, zper) as gram_launch / gram_kernel (csrc/pca.hip) pick them."""
-    ksplit = max(1, min(32, (num_cu * 8 + ntiles - 1) // ntiles))
-    if ksplit > Nz // 64:
-        ksplit = max(Nz // 64, 1)
-    zper = ((Nz + ksplit - 1) // ksplit + 3) & ~3
-    return ksplit, zper
-
-
 def gram_batch(widths, Nz, seed, slack=304):
     """Inputs of origin_pca_gram for matrices of n columns each (ld = n rounded up to 16): the
     concatenated [Nz][ld] blocks with columns n..ld zero (as the driver's gather leaves them) and

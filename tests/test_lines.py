@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import _line_oracle as oracle
+from _gram_geometry import gram_geometry, num_cu_of
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g11_lines.npz")
 
@@ -284,6 +285,32 @@ def test_estimator_against_the_oracle_in_one_and_two_batches(ctx, golden, Nz, P)
         assert np.array_equal(one[k], two[k]), k
     compare(lines.estimate_lines(ctx, f.cat, raw, var, f.psf), ref, device_tol(golden),
             f"Nz={Nz} P={P}")
+
+
+@pytest.mark.gpu
+def test_gram_groups_do_not_change_a_result(ctx):
+    """The (517, 9) shape at size_grid = 1: 97 problems of 6 Gram tiles each in one batch, more
+    than the largest Gram group that keeps a single problem's K-split (48 on a 256-CU device: three
+    groups; restated here from the launch rule for the device at hand), against one detection, and
+    so one group, per batch (max_problems = 9).  Bit for bit the same."""
+    from origin_amd import kernels
+    Nz, Ny, Nx, P = 517, 20, 22, 9
+    f = Field(Nz, Ny, Nx, P, scattered(np.random.default_rng(12), 12, Nz, Ny, Nx), seed=617)
+    nprob = int(kernels.lines_problem_counts(f.dets[:, 1], f.dets[:, 2], 1, Ny, Nx).sum())
+    num_cu, tiles = num_cu_of(ctx), 6    # ld = 96: the upper triangle of 3 x 3 tiles
+    ks1 = gram_geometry(num_cu, tiles, Nz)[0]
+    gmax = 1
+    while gmax < 1024 and gram_geometry(num_cu, (gmax + 1) * tiles, Nz)[0] == ks1:
+        gmax += 1
+    assert nprob > gmax, (nprob, gmax)
+    raw, var = f.device(ctx)
+    one = kernels.lines_estimate(ctx, raw, var, f.psf, None, *f.dets.T, size_grid=1)
+    assert one["nbatch"] == 1
+    many = kernels.lines_estimate(ctx, raw, var, f.psf, None, *f.dets.T, size_grid=1,
+                                  max_problems=9)
+    assert many["nbatch"] == 12
+    for k in ("line", "var", "flux5", "mse5", "yxz", "fallback"):
+        assert np.array_equal(one[k], many[k]), k
 
 
 @pytest.fixture(scope="module")
