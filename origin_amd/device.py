@@ -279,6 +279,18 @@ class DeviceArray:
                     strides=None)
 
 
+def copy_box(ctx, dst, dst_shape, dst_off, src, src_shape, src_off, box):
+    """device->device copy of an (nz, ny, nx) box between two arrays of one element type, read as
+    cubes of the given shapes (the strided form of ``DeviceArray.window``)."""
+    nz, ny, nx = box
+    es = src.dtype.itemsize
+    sp = src.ptr + ((src_off[0] * src_shape[1] + src_off[1]) * src_shape[2] + src_off[2]) * es
+    dp = dst.ptr + ((dst_off[0] * dst_shape[1] + dst_off[1]) * dst_shape[2] + dst_off[2]) * es
+    _capi.call("origin_copy_box", ctx.handle, 2, C.c_void_p(dp), dst_shape[2],
+               dst_shape[1] * dst_shape[2], C.c_void_p(sp), src_shape[2],
+               src_shape[1] * src_shape[2], nz, ny, nx, es)
+
+
 _default_ctx = {}
 
 

@@ -27,17 +27,18 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _capi, kernels
+from . import _capi, kernels, sparse
+from .device import copy_box
 
 Tile = namedtuple("Tile", "rank ty tx y0 y1 x0 x1")   # ty: row band, tx: position in the band
+R = 64    # side of the square regions the GLR's rectangles are made of
 
 
 def _split(n_units, parts):
     """Split n_units into `parts` contiguous groups whose sizes differ by at most one."""
     base, rem = divmod(n_units, parts)
     sizes = [base + (1 if i < rem else 0) for i in range(parts)]
-    edges = np.concatenate([[0], np.cumsum(sizes)])
-    return edges
+    return np.concatenate([[0], np.cumsum(sizes)])
 
 
 def _compositions(total, parts, lo=1):
@@ -51,15 +52,9 @@ def _compositions(total, parts, lo=1):
             yield (first,) + rest
 
 
-def grid_shape(world, nay=None, nax=None):
-    """gy x gx with gy*gx == world.  Without an area grid: as square as possible, gx >= gy.
-    With one (nay x nax areas): the factorisation whose fullest tile holds the fewest areas,
-    then the squarest, then gx >= gy."""
-    if nay is None or nax is None:
-        gy = int(np.floor(np.sqrt(world)))
-        while world % gy:
-            gy -= 1
-        return gy, world // gy
+def grid_shape(world, nay, nax):
+    """gy x gx with gy*gx == world on a grid of nay x nax areas: the factorisation whose fullest
+    tile holds the fewest areas, then the squarest, then gx >= gy."""
     best = None
     for gy in range(1, world + 1):
         if world % gy:
@@ -99,7 +94,45 @@ def band_layout(world, nay, nax):
     return best[1]
 
 
-class Tiling:
+class Partition:
+    """What ``Tiling`` and ``OwnerTiling`` share: the field (Ny, Nx), ``world`` ranks, the ``halo``
+    width and one ``Tile`` per rank -- the rank's rectangle, or the bounding box of its spaxels."""
+
+    def __init__(self, Ny, Nx, world, halo):
+        self.Ny, self.Nx, self.world, self.halo, self.tiles = Ny, Nx, world, halo, []
+
+    def tile(self, rank):
+        return self.tiles[rank]
+
+    def tile_shape(self, rank):
+        t = self.tiles[rank]
+        return t.y1 - t.y0, t.x1 - t.x0
+
+    def extended(self, rank):
+        """Extent of the tile plus its halo, clipped to the field: (y0, y1, x0, x1) and the
+        halo widths (top, bottom, left, right) actually present."""
+        t, h = self.tiles[rank], self.halo
+        top, bot = min(h, t.y0), min(h, self.Ny - t.y1)
+        left, right = min(h, t.x0), min(h, self.Nx - t.x1)
+        return (t.y0 - top, t.y1 + bot, t.x0 - left, t.x1 + right), (top, bot, left, right)
+
+    def ext_shape(self, rank):
+        """(e_ny, e_nx) of the extended box and its halo widths (top, bottom, left, right)."""
+        (y0, y1, x0, x1), halos = self.extended(rank)
+        return (y1 - y0, x1 - x0), halos
+
+    def owned_tile(self, rank):
+        """The rank's own spaxels among those of its tile (``owned_ext``: of its extended box): a
+        bool map, or None where the whole tile is the rank's, as in any partition into rectangles."""
+        return None
+    owned_ext = owned_tile
+
+    def check_halo(self):
+        """Raise if the halo cannot be served (an owner map serves any: columns come from whoever
+        owns them, however thin a rank's share is)."""
+
+
+class Tiling(Partition):
     """Partition of the field into one rectangle per rank, cut along the area grid (areas are
     area_size x area_size squares, the last one of a row / column absorbs the remainder, as
     synth.grid_areamap builds them), so that every PCA area lives on exactly one GPU.
@@ -108,9 +141,8 @@ class Tiling:
     layout="grid": a regular gy x gx grid (grid_shape) -- what rounds 1-2 used."""
 
     def __init__(self, Ny, Nx, world, area_size=100, halo=12, layout="bands"):
-        self.Ny, self.Nx, self.world, self.halo = Ny, Nx, world, halo
+        super().__init__(Ny, Nx, world, halo)
         nay, nax = max(1, Ny // area_size), max(1, Nx // area_size)
-        self.nay, self.nax, self.area_size = nay, nax, area_size
         if layout == "grid":
             gy, gx = grid_shape(world, nay, nax)
             rows = tuple(int(v) for v in np.diff(_split(nay, gy)))
@@ -120,7 +152,7 @@ class Tiling:
         else:
             raise ValueError("layout must be 'bands' or 'grid'")
         self.rows, self.ranks = rows, ranks
-        self.tiles, self._areas = [], []
+        self._areas = []
         ay0 = 0
         for ty, (h, nr) in enumerate(zip(rows, ranks)):
             y0 = ay0 * area_size
@@ -132,53 +164,30 @@ class Tiling:
                 self.tiles.append(Tile(len(self.tiles), ty, tx, y0, y1, x0, x1))
                 self._areas.append(h * int(ex[tx + 1] - ex[tx]))
             ay0 += h
-        # a regular grid is described by (gy, gx); other band layouts have no single gx
-        self.gy = len(rows)
-        self.gx = ranks[0] if len(set(ranks)) == 1 else None
-
-    def tile(self, rank):
-        return self.tiles[rank]
 
     def balance(self):
         """max / mean over the ranks of the tile's spaxels (DCT, GLR work) and of its areas (the
         PCA's work, to first order): what the tiling costs against an even split."""
-        spx = [float((t.y1 - t.y0) * (t.x1 - t.x0)) for t in self.tiles]
+        spx = [float(np.prod(self.tile_shape(r))) for r in range(self.world)]
         ar = [float(a) for a in self._areas]
         return dict(spaxels=float(max(spx) / np.mean(spx)), areas=float(max(ar) / np.mean(ar)),
                     rows_per_band=[int(v) for v in self.rows],
                     ranks_per_band=[int(v) for v in self.ranks])
 
-    def extended(self, rank):
-        """Extent of the tile plus its halo, clipped to the field: (y0, y1, x0, x1) and the
-        halo widths (top, bottom, left, right) actually present."""
-        t, h = self.tiles[rank], self.halo
-        top = min(h, t.y0)
-        bot = min(h, self.Ny - t.y1)
-        left = min(h, t.x0)
-        right = min(h, self.Nx - t.x1)
-        return (t.y0 - top, t.y1 + bot, t.x0 - left, t.x1 + right), (top, bot, left, right)
-
-    def min_tile_side(self):
-        return min(min(t.y1 - t.y0, t.x1 - t.x0) for t in self.tiles)
-
     def check_halo(self):
         # a strip must come from ONE neighbour: every tile at least a halo wide
-        if self.min_tile_side() < self.halo:
+        if min(min(self.tile_shape(r)) for r in range(self.world)) < self.halo:
             raise ValueError(f"a tile is narrower than the halo {self.halo}: a halo must come "
                              "from the tiles next to this one, not from beyond them")
-
-    def owned_ext(self, rank):
-        """None: every spaxel of the tile (the interior of the extended box) is this rank's."""
-        return None
 
     def local_regions(self, rank, reach, R=64):
         """Bool array over the R x R regions of the extended tile: True where the region's GLR
         reads no spaxel of another rank (interior_regions)."""
-        (y0, y1, x0, x1), halos = self.extended(rank)
-        return interior_regions(y1 - y0, x1 - x0, halos, reach, R)
+        (e_ny, e_nx), halos = self.ext_shape(rank)
+        return interior_regions(e_ny, e_nx, halos, reach, R)
 
 
-class OwnerTiling:
+class OwnerTiling(Partition):
     """Partition of the field by an OWNER MAP: ``owner[y, x]`` = the rank that keeps spaxel
     (y, x).  What a field cut along irregular PCA areas needs (reference steps.py:492-569: areas
     come out of a segmentation, convex hulls and growing, not off a grid): every area goes to one
@@ -188,16 +197,15 @@ class OwnerTiling:
     distance) of an owned one -- they arrive as lists of spaxel columns from their owners
     (``column_plan`` / ``exchange_columns``); the rest of the box never influences a kept result.
 
-    Same accessors as ``Tiling`` (tile, extended, halo, balance) so that ``TiledGLR`` takes either.
+    ``owned_tile`` / ``owned_ext`` are bool maps here and None ("all mine") on a ``Tiling``.
     """
 
     def __init__(self, owner, world, halo, n_areas=None):
         owner = np.ascontiguousarray(owner).astype(np.int32)
         if owner.ndim != 2 or owner.min() < 0 or owner.max() >= world:
             raise ValueError("owner must be a (Ny, Nx) map of ranks 0 .. world - 1")
-        self.owner, self.world, self.halo = owner, int(world), int(halo)
-        self.Ny, self.Nx = owner.shape
-        self.tiles, self._count = [], []
+        super().__init__(*owner.shape, int(world), int(halo))
+        self.owner, self._count = owner, []
         for r in range(world):
             rows = np.flatnonzero((owner == r).any(axis=1))
             cols = np.flatnonzero((owner == r).any(axis=0))
@@ -267,26 +275,12 @@ class OwnerTiling:
         t.rank_of_label = {int(l): int(r) for l, r in zip(labels, rank_of)}
         return t
 
-    # -- Tiling's accessors --------------------------------------------------------
-    def tile(self, rank):
-        return self.tiles[rank]
-
-    def extended(self, rank):
-        t, h = self.tiles[rank], self.halo
-        top, bot = min(h, t.y0), min(h, self.Ny - t.y1)
-        left, right = min(h, t.x0), min(h, self.Nx - t.x1)
-        return (t.y0 - top, t.y1 + bot, t.x0 - left, t.x1 + right), (top, bot, left, right)
-
-    def check_halo(self):
-        pass    # (columns come from whoever owns them, however thin a rank's share is)
-
     def balance(self):
         """max / mean over the ranks of the owned spaxels (what the areas cost the PCA, to first
         order), of the areas, and of the extended boxes (what DCT-free stages -- GLR, local
         maxima -- run on: a box also holds spaxels of other ranks)."""
         own = np.array(self._count, dtype=float)
-        box = np.array([float((e[1] - e[0]) * (e[3] - e[2]))
-                        for e in (self.extended(r)[0] for r in range(self.world))])
+        box = np.array([float(np.prod(self.ext_shape(r)[0])) for r in range(self.world)])
         ar = np.array(self._areas, dtype=float)
         return dict(spaxels=float(own.max() / own.mean()), areas=float(ar.max() / ar.mean()),
                     boxes=float(box.max() / box.mean()),
@@ -322,7 +316,7 @@ class OwnerTiling:
         own = self.owned_ext(rank)
         e_ny, e_nx = own.shape
         nry, nrx = (e_ny + R - 1) // R, (e_nx + R - 1) // R
-        (y0, y1, x0, x1), _ = self.extended(rank)
+        y0, y1, x0, x1 = self.extended(rank)[0]
         ok = np.zeros((nry, nrx), bool)
         for ry in range(nry):
             a, b = R * ry - reach, min(e_ny, R * ry + R) + reach
@@ -353,7 +347,7 @@ class TileComm:
       created on ANY rank, EVERY rank raises: there is no silent change of transport.
     * ``backend="host"``: strips are staged through host memory and the host group (CPU
       tests; one-GPU rehearsal with several ranks on the same card, which RCCL refuses).
-      Only on request.  (``"gloo"``, the name rounds 1-2 used, is accepted as an alias.)
+      Only on request.
     """
 
     def __init__(self, rank, world, local_rank, backend=None, group=None):
@@ -361,7 +355,7 @@ class TileComm:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29577")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC for RCCL
-        backend = {None: "rccl", "gloo": "host"}.get(backend, backend)
+        backend = "rccl" if backend is None else backend
         if backend not in ("rccl", "host"):
             raise ValueError(f"backend must be 'rccl' or 'host', not {backend!r}")
         self.note = ""
@@ -371,7 +365,6 @@ class TileComm:
         self.group = group
         self._want_rccl = backend == "rccl"
         self._native = None          # origin_comm* once attached
-        self._ctx = None
         self.backend = backend
 
     @property
@@ -415,7 +408,7 @@ class TileComm:
             except Exception as exc:  # noqa: BLE001
                 err = str(exc)
         if self.group.allreduce(np.array([ok]), "min")[0] == 1.0:
-            self._native, self._ctx = handle, ctx
+            self._native = handle
             return
         if ok:
             _capi.call("origin_comm_destroy", handle)
@@ -484,23 +477,11 @@ def init_comm(rank, world, local_rank, backend=None, group=None):
     return TileComm(rank, world, local_rank, backend, group)
 
 
-# names of rounds 1-2, kept as aliases (deprecated: use TileComm / Tiling)
-TorchComm = TileComm
-
-
-# ------------------------------------------------------------------------------- halo
-def _copy_box(ctx, dst, dst_shape, dst_off, src, src_shape, src_off, box):
-    """device->device copy of an (nz, ny, nx) box between float32 cubes of the given shapes."""
-    nz, ny, nx = box
-    es = src.dtype.itemsize
-    sp = src.ptr + ((src_off[0] * src_shape[1] + src_off[1]) * src_shape[2] + src_off[2]) * es
-    dp = dst.ptr + ((dst_off[0] * dst_shape[1] + dst_off[1]) * dst_shape[2] + dst_off[2]) * es
-    import ctypes as C
-    _capi.call("origin_copy_box", ctx.handle, 2, C.c_void_p(dp), dst_shape[2],
-               dst_shape[1] * dst_shape[2], C.c_void_p(sp), src_shape[2],
-               src_shape[1] * src_shape[2], nz, ny, nx, es)
-
-
+# ------------------------------------------------------------------------------- exchange
+# An exchange plan is (sends, recvs, local).  sends / recvs: lists of (peer, piece), ordered by
+# peer; a piece is a box ((oy, ox), (by, bx)) or a flat int32 list of spaxel indices, in the
+# coordinates of the array it is cut from / put into.  local: None, or the (source piece,
+# destination piece) of what stays on the rank.
 def halo_plan(tiling, rank):
     """The halo exchange of one rank as plain index boxes (no data), ONE phase for any partition
     into rectangles: rank r sends to every other rank t the part of its own tile that lies inside
@@ -530,48 +511,6 @@ def halo_plan(tiling, rank):
     return sends, recvs
 
 
-def exchange_halo(ctx, comm, tiling, rank, cube, ext=None, bufs=None):
-    """Fill the halo of this rank's extended device tile (Nz, ny + top + bot, nx + left + right).
-    ``cube``: the bare (Nz, ny, nx) tile, copied into the interior first -- or None when the
-    interior of ``ext`` already holds it (the greedy PCA can write there directly).  ``bufs``: a
-    dict the caller keeps between calls so that the strip buffers are allocated once.  Any
-    element type (float32 cubes, the uint8 mask); with an ``OwnerTiling`` the halo is the list of
-    spaxel columns of ``column_plan`` instead of strips."""
-    t = tiling.tile(rank)
-    ny, nx = t.y1 - t.y0, t.x1 - t.x0
-    (_, _, _, _), (top, bot, left, right) = tiling.extended(rank)
-    Nz = (cube if cube is not None else ext).shape[0]
-    eshape = (Nz, ny + top + bot, nx + left + right)
-    dtype = (cube if cube is not None else ext).dtype
-    if ext is None:
-        ext = ctx.zeros(eshape, dtype)
-    if cube is not None:
-        _copy_box(ctx, ext, eshape, (0, top, left), cube, cube.shape, (0, 0, 0), (Nz, ny, nx))
-    if isinstance(tiling, OwnerTiling):
-        return exchange_columns(ctx, comm, tiling, rank, ext, bufs)
-    plan_s, plan_r = halo_plan(tiling, rank)
-    sends, recvs, unpack = [], [], []
-    for kind, items in (("s", plan_s), ("r", plan_r)):
-        for peer, (oy, ox), (by, bx) in items:
-            key = (kind, peer, Nz, by, bx, dtype.str)
-            buf = bufs.get(key) if bufs is not None else None
-            if buf is None:
-                buf = ctx.empty((Nz, by, bx), dtype)
-                if bufs is not None:
-                    bufs[key] = buf
-            if kind == "s":   # cut from the interior of ext (tile coordinates + halo offset)
-                _copy_box(ctx, buf, buf.shape, (0, 0, 0), ext, eshape, (0, top + oy, left + ox),
-                          (Nz, by, bx))
-                sends.append((peer, buf))
-            else:
-                recvs.append((peer, buf))
-                unpack.append((buf, (0, oy, ox), (Nz, by, bx)))
-    comm.exchange(ctx, sends, recvs)
-    for rbuf, off, box in unpack:
-        _copy_box(ctx, ext, eshape, off, rbuf, rbuf.shape, (0, 0, 0), box)
-    return ext
-
-
 def column_plan(tiling, rank):
     """The exchange of one rank of an ``OwnerTiling`` as index lists (no data): rank r sends every
     other rank t the columns of its own spaxels that t needs (``tiling.needed(t)``) and receives
@@ -595,66 +534,156 @@ def column_plan(tiling, rank):
     return sends, recvs
 
 
-def exchange_columns(ctx, comm, tiling, rank, ext, bufs=None):
-    """Halo exchange of an ``OwnerTiling``: gather the columns the peers need from this rank's
-    extended device tile, exchange, scatter what arrives (origin_gather_columns /
-    origin_scatter_columns).  The owned part of ``ext`` must be in place."""
-    Nz, e_ny, e_nx = ext.shape
-    bufs = {} if bufs is None else bufs
-    plan = bufs.get(("plan", rank))
-    if plan is None:
-        ps, pr = column_plan(tiling, rank)
-        plan = bufs[("plan", rank)] = (
-            [(peer, ctx.to_device(ix)) for peer, ix in ps],
-            [(peer, ctx.to_device(ix)) for peer, ix in pr])
-    es = ext.dtype.itemsize
-    S = e_ny * e_nx
+def move_plan(src_tiling, dst_tiling, rank):
+    """The move of a cube from one ``OwnerTiling`` to another as index lists (no data): rank r
+    sends every other rank t the columns it owns in ``src_tiling`` that t owns in ``dst_tiling``.
+    Returns (sends, recvs, local): sends index this rank's TILE in ``src_tiling``, recvs its tile
+    in ``dst_tiling``; ``local`` = (indices in the source tile, indices in the destination tile)
+    of the columns that stay on this rank, or None.  All in C order of the field."""
+    st, dt = src_tiling.tile(rank), dst_tiling.tile(rank)
+    mine_src, mine_dst = src_tiling.owner == rank, dst_tiling.owner == rank
 
-    def packed(kind, peer, n):
-        key = (kind, peer, Nz, n, ext.dtype.str)
-        b = bufs.get(key)
+    def lists(mine, theirs, t):
+        out = []
+        for other in range(src_tiling.world):
+            ys, xs = np.nonzero(mine & (theirs == other))
+            if len(ys):
+                out.append((other, ((ys - t.y0) * (t.x1 - t.x0) + (xs - t.x0)).astype(np.int32)))
+        return out
+    sends, recvs = lists(mine_src, dst_tiling.owner, st), lists(mine_dst, src_tiling.owner, dt)
+    local = [ix for items in (sends, recvs) for peer, ix in items if peer == rank]
+    return ([s for s in sends if s[0] != rank], [r for r in recvs if r[0] != rank],
+            tuple(local) if local else None)
+
+
+def _halo_pieces(tiling, rank):
+    """The halo plan of either partition class with every piece in EXTENDED coordinates."""
+    if isinstance(tiling, OwnerTiling):
+        return column_plan(tiling, rank) + (None,)
+    sends, recvs = halo_plan(tiling, rank)
+    top, _, left, _ = tiling.extended(rank)[1]
+    return ([(peer, ((top + oy, left + ox), size)) for peer, (oy, ox), size in sends],
+            [(peer, (off, size)) for peer, off, size in recvs], None)
+
+
+def _piece_shape(Nz, piece):
+    return (Nz,) + (piece[1] if isinstance(piece, tuple) else (piece.size,))
+
+
+def _copy_piece(ctx, arr, piece, buf, pack):
+    """``pack``: a piece of the (Nz, ny, nx) device array ``arr`` into the contiguous ``buf``;
+    otherwise ``buf`` into that piece of ``arr``."""
+    Nz = arr.shape[0]
+    if isinstance(piece, tuple):
+        (oy, ox), (by, bx) = piece
+        there, here = (arr, arr.shape, (0, oy, ox)), (buf, buf.shape, (0, 0, 0))
+        copy_box(ctx, *(here + there if pack else there + here), (Nz, by, bx))
+    else:
+        _capi.call("origin_gather_columns" if pack else "origin_scatter_columns", ctx.handle,
+                   arr.p, Nz, arr.size // Nz, piece.p, piece.size, arr.dtype.itemsize, buf.p)
+
+
+def exchange_pieces(ctx, comm, src, dst, key, make_plan, bufs):
+    """THE device exchange: pack every send piece of ``src`` into a buffer, ``comm.exchange``,
+    unpack every received piece into ``dst`` (both (Nz, ny, nx) DeviceArrays of one dtype; boxes
+    through origin_copy_box, index lists through origin_gather_columns / origin_scatter_columns).
+    What stays on the rank moves first.  ``bufs``: the caller's dict.  It keeps the plan
+    ``make_plan()`` returned (under ``key``, its index lists uploaded once) and every buffer, so
+    nothing here is freed before the stream has run the last unpack as long as the caller holds
+    the dict until then."""
+    plan = bufs.get(key)
+    if plan is None:
+        def dev(piece):
+            return piece if isinstance(piece, tuple) else ctx.to_device(piece)
+        sends, recvs, local = make_plan()
+        plan = bufs[key] = ([(peer, dev(pc)) for peer, pc in sends],
+                            [(peer, dev(pc)) for peer, pc in recvs],
+                            None if local is None else (dev(local[0]), dev(local[1])))
+    sends, recvs, local = plan
+    Nz = src.shape[0]
+
+    def buffer(kind, peer, piece):
+        k = (kind, peer, _piece_shape(Nz, piece), src.dtype.str)
+        b = bufs.get(k)
         if b is None:
-            b = bufs[key] = ctx.empty((Nz, n), ext.dtype)
+            b = bufs[k] = ctx.empty(k[2], src.dtype)
         return b
-    sends, recvs = [], []
-    for peer, ix in plan[0]:
-        b = packed("cs", peer, ix.size)
-        _capi.call("origin_gather_columns", ctx.handle, ext.p, Nz, S, ix.p, ix.size, es, b.p)
-        sends.append((peer, b))
-    for peer, ix in plan[1]:
-        recvs.append((peer, packed("cr", peer, ix.size)))
-    comm.exchange(ctx, sends, recvs)
-    for (peer, ix), (_, b) in zip(plan[1], recvs):
-        _capi.call("origin_scatter_columns", ctx.handle, ext.p, Nz, S, ix.p, ix.size, es, b.p)
-    return ext
+    if local is not None:
+        b = buffer("l", None, local[0])
+        _copy_piece(ctx, src, local[0], b, True)
+        _copy_piece(ctx, dst, local[1], b, False)
+    out = []
+    for peer, piece in sends:
+        out.append((peer, buffer("s", peer, piece)))
+        _copy_piece(ctx, src, piece, out[-1][1], True)
+    inn = [(peer, buffer("r", peer, piece)) for peer, piece in recvs]
+    comm.exchange(ctx, out, inn)
+    for (_, piece), (_, b) in zip(recvs, inn):
+        _copy_piece(ctx, dst, piece, b, False)
+    return dst
+
+
+def exchange_pieces_host(group, src, dst, plan):
+    """The same on host ndarrays over a host group (nothing to keep: no buffers, no uploads)."""
+    Nz = src.shape[0]
+
+    def cut(piece):
+        if isinstance(piece, tuple):
+            (oy, ox), (by, bx) = piece
+            return np.ascontiguousarray(src[:, oy: oy + by, ox: ox + bx])
+        return np.ascontiguousarray(src.reshape(Nz, -1)[:, piece])
+
+    def put(piece, b):
+        if isinstance(piece, tuple):
+            (oy, ox), (by, bx) = piece
+            dst[:, oy: oy + by, ox: ox + bx] = b
+        else:
+            dst.reshape(Nz, -1)[:, piece] = b
+    sends, recvs, local = plan
+    if local is not None:
+        put(local[1], cut(local[0]))
+    out = [(peer, cut(piece)) for peer, piece in sends]
+    inn = [(peer, np.empty(_piece_shape(Nz, piece), dtype=dst.dtype)) for peer, piece in recvs]
+    if out or inn:
+        group.exchange(out, inn)
+    for (_, piece), (_, b) in zip(recvs, inn):
+        put(piece, b)
+    return dst
+
+
+def exchange_halo(ctx, comm, tiling, rank, cube, ext=None, bufs=None):
+    """Fill the halo of this rank's extended device tile (Nz, ny + top + bot, nx + left + right).
+    ``cube``: the bare (Nz, ny, nx) tile, copied into the interior first -- or None when the
+    interior of ``ext`` already holds it (the greedy PCA can write there directly).  ``bufs``: a
+    dict the caller keeps between calls so that the strip buffers are allocated once.  Any
+    element type (float32 cubes, the uint8 mask); with an ``OwnerTiling`` the halo is the list of
+    spaxel columns of ``column_plan`` instead of strips."""
+    ny, nx = tiling.tile_shape(rank)
+    (e_ny, e_nx), (top, _, left, _) = tiling.ext_shape(rank)
+    like = cube if cube is not None else ext
+    Nz = like.shape[0]
+    if ext is None:
+        ext = ctx.zeros((Nz, e_ny, e_nx), like.dtype)
+    if cube is not None:
+        copy_box(ctx, ext, ext.shape, (0, top, left), cube, cube.shape, (0, 0, 0), (Nz, ny, nx))
+    return exchange_pieces(ctx, comm, ext, ext, ("plan", tiling, rank),
+                           lambda: _halo_pieces(tiling, rank), {} if bufs is None else bufs)
+
+
+def exchange_columns(ctx, comm, tiling, rank, ext, bufs=None):
+    """Halo exchange of an ``OwnerTiling`` on its extended device tile, whose owned part must be
+    in place: ``exchange_halo(..., None, ext, bufs)``."""
+    return exchange_halo(ctx, comm, tiling, rank, None, ext, bufs)
 
 
 def exchange_halo_host(comm, tiling, rank, tile):
     """Same exchange on host ndarrays (float64 allowed) -- used by the CPU tests to check the
     tiling arithmetic against the untiled oracle."""
     Nz, ny, nx = tile.shape
-    (_, _, _, _), (top, bot, left, right) = tiling.extended(rank)
-    ext = np.zeros((Nz, ny + top + bot, nx + left + right), dtype=tile.dtype)
+    (e_ny, e_nx), (top, _, left, _) = tiling.ext_shape(rank)
+    ext = np.zeros((Nz, e_ny, e_nx), dtype=tile.dtype)
     ext[:, top: top + ny, left: left + nx] = tile
-    if isinstance(tiling, OwnerTiling):
-        ps, pr = column_plan(tiling, rank)
-        flat = ext.reshape(Nz, -1)
-        sends = [(peer, np.ascontiguousarray(flat[:, ix])) for peer, ix in ps]
-        recvs = [(peer, np.empty((Nz, len(ix)), dtype=tile.dtype)) for peer, ix in pr]
-        if sends or recvs:
-            comm.group.exchange(sends, recvs)
-        for (peer, ix), (_, rbuf) in zip(pr, recvs):
-            flat[:, ix] = rbuf
-        return ext
-    plan_s, plan_r = halo_plan(tiling, rank)
-    sends = [(peer, np.ascontiguousarray(tile[:, oy: oy + by, ox: ox + bx]))
-             for peer, (oy, ox), (by, bx) in plan_s]
-    recvs = [(peer, np.empty((Nz, by, bx), dtype=tile.dtype)) for peer, _, (by, bx) in plan_r]
-    if sends or recvs:
-        comm.group.exchange(sends, recvs)
-    for (peer, (oy, ox), (by, bx)), (_, rbuf) in zip(plan_r, recvs):
-        ext[:, oy: oy + by, ox: ox + bx] = rbuf
-    return ext
+    return exchange_pieces_host(comm.group, ext, ext, _halo_pieces(tiling, rank))
 
 
 def region_rects(ok, Ny, Nx, R=64):
@@ -725,14 +754,12 @@ class TiledGLR:
             raise ValueError(f"tiling halo {tiling.halo} is smaller than the PSF half width {need}")
         tiling.check_halo()
         (y0, y1, x0, x1), self.halos = tiling.extended(rank)
-        self.eshape = (Nz, y1 - y0, x1 - x0)
+        self.eshape, self.shape = (Nz, y1 - y0, x1 - x0), (Nz,) + tiling.tile_shape(rank)
         wext = None
         if weights is not None:
             wext = [np.ascontiguousarray(np.asarray(w, dtype=np.float64)[y0:y1, x0:x1])
                     for w in weights]
         self.plan = kernels.GLRPlan(ctx, self.eshape, PSF, wext, profiles, pcut, pmeansub)
-        t = tiling.tile(rank)
-        self.shape = (Nz, t.y1 - t.y0, t.x1 - t.x0)
         # (zeros: with an OwnerTiling the box also holds spaxels that are neither this rank's nor
         # needed by it; nothing kept depends on them, but they should not be NaN patterns)
         if ext is not None and (ext.shape != self.eshape or ext.dtype != np.float32):
@@ -748,6 +775,7 @@ class TiledGLR:
         self._early_done = None   # regions whose GLR the tail hook has started (this step)
         self._strips = {}
         self._lm = None   # extended local-maxima cubes, allocated by the first run that wants them
+        self._lm_sparse = None   # (and their sparse form's buffers)
 
     def faint_target(self):
         """``into`` argument of pipeline.greedy_pca: the interior of the extended tile.  A PCA run
@@ -775,6 +803,32 @@ class TiledGLR:
             self._mask_set = True
         return self.emask if mask is not None else None
 
+    def _split_regions(self, interior, done=None, busy=(), budget=None):
+        """The R x R regions of the extended tile as two bool maps (ahead, behind).  ahead: the
+        regions whose GLR can start before the halo has arrived -- they read no spaxel of another
+        rank (``interior``; False: none does), no row / column within the PSF's reach of a
+        ``busy`` box ((ymin, ymax, xmin, xmax) in TILE coordinates, inclusive), they are not
+        ``done`` already, and they are the first in row order up to ``budget`` voxels.  behind:
+        whatever is neither ahead nor done."""
+        top, _, left, _ = self.halos
+        reach = self.plan.P // 2
+        ahead = self.tiling.local_regions(self.rank, reach, R)
+        if not interior:
+            ahead[:] = False
+        for ymin, ymax, xmin, xmax in busy:
+            r0, r1 = max(0, (ymin + top - reach) // R), (ymax + top + reach) // R
+            c0, c1 = max(0, (xmin + left - reach) // R), (xmax + left + reach) // R
+            ahead[r0:r1 + 1, c0:c1 + 1] = False
+        if done is not None:
+            ahead &= ~done
+        if budget is not None:
+            keep = max(1, int(budget / (self.Nz * R * R)))
+            ahead.reshape(-1)[np.flatnonzero(ahead)[keep:]] = False
+        return ahead, ~ahead if done is None else ~ahead & ~done
+
+    def _rects(self, regions):
+        return region_rects(regions, self.eshape[1], self.eshape[2], R)
+
     def make_tail_hook(self, area_boxes, mask, early_budget=8.5e8):
         """A function for ``Context.set_pca_tail_hook`` around the greedy PCA that writes this
         tile (``into=faint_target()``): when few areas still iterate, the regions of the extended
@@ -786,24 +840,11 @@ class TiledGLR:
         self._set_mask(mask)   # (collective: here, on every rank, not inside the hook)
         if not self.plan.rows_supported():
             return None
-        top, _, left, _ = self.halos
-        e_ny, e_nx = self.eshape[1:]
-        reach = self.plan.P // 2
 
         def hook(areas):
-            ok = self.tiling.local_regions(self.rank, reach)
-            for a in areas:
-                if area_boxes[a] is None:
-                    continue
-                ymin, ymax, xmin, xmax = area_boxes[a]
-                r0, r1 = max(0, (ymin + top - reach) // 64), (ymax + top + reach) // 64
-                c0, c1 = max(0, (xmin + left - reach) // 64), (xmax + left + reach) // 64
-                ok[r0:r1 + 1, c0:c1 + 1] = False
-            if early_budget is not None:     # the first regions in row order, up to the budget
-                keep = max(1, int(early_budget / (self.Nz * 64 * 64)))
-                flat = np.flatnonzero(ok)
-                ok.reshape(-1)[flat[keep:]] = False
-            rects = region_rects(ok, e_ny, e_nx)
+            busy = [area_boxes[a] for a in areas if area_boxes[a] is not None]
+            ahead, _ = self._split_regions(True, busy=busy, budget=early_budget)
+            rects = self._rects(ahead)
             if not rects:
                 return
             emask = self._set_mask(mask)
@@ -811,7 +852,7 @@ class TiledGLR:
             for i, (y0, y1, x0, x1) in enumerate(rects):
                 self.plan.run_rect(self.ext, emask, oc, op, om, y0, y1, x0, x1, first=(i == 0),
                                    side=True)
-            self._early_done = ok
+            self._early_done = ahead
         return hook
 
     def run(self, cube_faint, mask, correl, profile, correl_min, local_max=None, size=3,
@@ -838,111 +879,118 @@ class TiledGLR:
         ``compute_local_max(correl, correl_min, mask, size)`` (reference steps.py:796).  The
         maximum filter looks size // 2 spaxels beyond the tile, so the tiling's halo must be at
         least P // 2 + size // 2: those neighbours are then exact values of the extended GLR."""
-        ctx = self.ctx
-        top, bot, left, right = self.halos
-        Nz, ny, nx = self.shape
+        done, self._early_done = self._early_done, None   # (regions the tail hook started)
+        self._check_args(cube_faint, done, correl, profile, correl_min, local_max, size)
         emask = self._set_mask(mask)
-        # Interior first: the regions of the extended tile whose GLR reads no halo data run on the
-        # context's side stream WHILE the strips travel (and while this rank waits for a neighbour
-        # that is still iterating); the regions along the halo follow the exchange on the main
-        # stream.  Needs the tile in self.ext already (cube_faint None: the PCA wrote it there)
-        # and a plan whose stages take rectangles; ORIGIN_TILED_INTERIOR_FIRST=0 turns it off.
-        early, done = [], self._early_done   # (done: regions the tail hook started, this step)
-        self._early_done = None
+        rects = self._pick_rects(cube_faint, done)
+        o = self._glr(cube_faint, emask, rects, done is None, before_exchange)
+        res = self._hand_out(o, correl, profile, correl_min)
+        if local_max is not None and local_max is not False:
+            res["local_max"], res["local_min"] = self._local_maxima(o, emask, local_max, size)
+        return res
+
+    def _check_args(self, cube_faint, done, correl, profile, correl_min, local_max, size):
+        """Everything ``run`` can refuse, before any rank enters a collective."""
         if cube_faint is not None and done is not None:
             raise ValueError("the tail hook started this step's GLR on the extended tile: "
                              "run(None, ...) must finish it")
-        if (cube_faint is None and self.plan.rows_supported()
-                and (done is not None
-                     or os.environ.get("ORIGIN_TILED_INTERIOR_FIRST", "1") != "0")):
-            e_ny, e_nx = self.eshape[1:]
-            ok = self.tiling.local_regions(self.rank, self.plan.P // 2)
-            if os.environ.get("ORIGIN_TILED_INTERIOR_FIRST", "1") == "0":
-                ok[:] = False                 # (only what the hook started runs ahead)
-            if done is not None:
-                ok |= done
-            late = region_rects(~ok, e_ny, e_nx)
-            early = region_rects(ok & ~done if done is not None else ok, e_ny, e_nx)
-            if not early and done is not None:
-                early = [None]                # (nothing more ahead, but the step is in rectangles)
-        if early:
-            oc, op, om = self.out["correl"], self.out["profile"], self.out["correl_min"]
-            for i, rect in enumerate(r for r in early if r is not None):
-                y0, y1, x0, x1 = rect
-                self.plan.run_rect(self.ext, emask, oc, op, om, y0, y1, x0, x1,
-                                   first=(i == 0 and done is None), side=True)
-            early = [r for r in early if r is not None]
-            if before_exchange is not None:
-                before_exchange()
-            exchange_halo(ctx, self.comm, self.tiling, self.rank, None, self.ext, self._strips)
-            for y0, y1, x0, x1 in late:
-                self.plan.run_rect(self.ext, emask, oc, op, om, y0, y1, x0, x1)
-            maxmap, minmap = self.plan.run_finish(want_maps=True)
-            o = dict(correl=oc, profile=op, correl_min=om, maxmap=maxmap, minmap=minmap)
-        else:
-            # cube_faint None: the greedy PCA wrote this step's tile straight into self.ext's
-            # interior
-            if before_exchange is not None:
-                before_exchange()
-            exchange_halo(ctx, self.comm, self.tiling, self.rank, cube_faint, self.ext,
-                          self._strips)
-            o = self.plan.run(self.ext, mask=emask, correl=self.out["correl"],
-                              profile=self.out["profile"], correl_min=self.out["correl_min"],
-                              want_maps=True)
-        self.last_rects = (early, late if (early or done is not None) else [],
-                           0 if done is None else int(done.sum()))
+        crop = correl is not None
+        if not crop and (profile is not None or correl_min is not None):
+            raise ValueError("pass all three output cubes or none of them")
+        if local_max is None or local_max is False:
+            return
+        need = self.plan.P // 2 + int(size) // 2
+        if self.tiling.halo < need:
+            raise ValueError(f"local maxima of size {size} on tiles need a halo of {need} "
+                             f"spaxels, the tiling has {self.tiling.halo}")
+        if local_max == "sparse":
+            if crop:
+                raise ValueError("local_max='sparse' goes with correl=None (no crop at all)")
+            if int(size) != 3 or sparse.plan(self.ctx, self.eshape)[0] == 0:
+                raise ValueError("no sparse local-maximum form for this tile (size 3, Nx % 4)")
+        elif local_max is True and crop:
+            raise ValueError("local_max=True goes with correl=None (no crop at all)")
+
+    def _pick_rects(self, cube_faint, done):
+        """Stage 1: (ahead, behind) -- the rectangles whose GLR runs before the halo exchange, on
+        the context's side stream WHILE the strips travel (and while this rank waits for a
+        neighbour that is still iterating), and those that follow it on the main stream; or None:
+        one GLR of the whole extended tile behind the exchange.  Rectangles need the tile in
+        self.ext already (cube_faint None: the PCA wrote it there) and a plan whose stages take
+        them; ORIGIN_TILED_INTERIOR_FIRST=0 leaves only what the hook started ahead."""
+        interior = os.environ.get("ORIGIN_TILED_INTERIOR_FIRST", "1") != "0"
+        rects = None
+        if cube_faint is None and self.plan.rows_supported() and (done is not None or interior):
+            ahead, behind = self._split_regions(interior, done)
+            rects = (self._rects(ahead), self._rects(behind))
+            if not rects[0] and done is None:
+                rects = None              # (nothing runs ahead: no reason to cut the step up)
+        ahead, behind = rects or ([], [])
+        self.last_rects = (ahead, behind, 0 if done is None else int(done.sum()))
+        return rects
+
+    def _glr(self, cube_faint, emask, rects, first, before_exchange):
+        """Stage 2: the GLR of the step on the extended tile, around the halo exchange (``rects``
+        of _pick_rects) or behind it; ``first``: no rectangle of this step has run yet (the tail
+        hook started none).  Returns the extended outputs and maps."""
+        oc, op, om = self.out["correl"], self.out["profile"], self.out["correl_min"]
+        for i, (y0, y1, x0, x1) in enumerate(rects[0] if rects else ()):
+            self.plan.run_rect(self.ext, emask, oc, op, om, y0, y1, x0, x1,
+                               first=(i == 0 and first), side=True)
+        if before_exchange is not None:
+            before_exchange()
+        # cube_faint None: the greedy PCA wrote this step's tile straight into self.ext's interior
+        exchange_halo(self.ctx, self.comm, self.tiling, self.rank, cube_faint, self.ext,
+                      self._strips)
+        if rects is None:
+            return self.plan.run(self.ext, mask=emask, correl=oc, profile=op, correl_min=om,
+                                 want_maps=True)
+        for y0, y1, x0, x1 in rects[1]:
+            self.plan.run_rect(self.ext, emask, oc, op, om, y0, y1, x0, x1)
+        maxmap, minmap = self.plan.run_finish(want_maps=True)
+        return dict(correl=oc, profile=op, correl_min=om, maxmap=maxmap, minmap=minmap)
+
+    def _hand_out(self, o, correl, profile, correl_min):
+        """Stage 3: the three cubes cropped into the caller's arrays -- or the extended ones as
+        they are -- and the maps of the kept spaxels, cropped on the device (no host round trip
+        per step)."""
+        ctx = self.ctx
+        top, _, left, _ = self.halos
+        Nz, ny, nx = self.shape
         crop = correl is not None
         if crop:
             for name, dst in (("correl", correl), ("correl_min", correl_min), ("profile", profile)):
-                _copy_box(ctx, dst, dst.shape, (0, 0, 0), o[name], self.eshape, (0, top, left),
-                          (Nz, ny, nx))
+                copy_box(ctx, dst, dst.shape, (0, 0, 0), o[name], self.eshape, (0, top, left),
+                         (Nz, ny, nx))
         else:
-            if profile is not None or correl_min is not None:
-                raise ValueError("pass all three output cubes or none of them")
             correl, correl_min, profile = o["correl"], o["correl_min"], o["profile"]
-        # the maps of the kept spaxels, cropped on the device (no host round trip per step)
-        e_ny, e_nx = self.eshape[1:]
         for name in ("maxmap", "minmap"):
-            _copy_box(ctx, self.maps[name], (1, ny, nx), (0, 0, 0), o[name], (1, e_ny, e_nx),
-                      (0, top, left), (1, ny, nx))
-        res = dict(correl=correl, profile=profile, correl_min=correl_min,
-                   maxmap=self.maps["maxmap"], minmap=self.maps["minmap"],
-                   box=(top, left, ny, nx) if not crop else (0, 0, ny, nx),
-                   # OwnerTiling: which spaxels of the box are this rank's (None: all of them)
-                   owned=(None if self.tiling.owned_ext(self.rank) is None else
-                          self.tiling.owned_ext(self.rank)[top:top + ny, left:left + nx]))
-        if local_max is not None and local_max is not False:
-            need = self.plan.P // 2 + int(size) // 2
-            if self.tiling.halo < need:
-                raise ValueError(f"local maxima of size {size} on tiles need a halo of {need} "
-                                 f"spaxels, the tiling has {self.tiling.halo}")
-            if local_max == "sparse":
-                # (index, value) lists of the extended cubes' non-zero voxels instead of two dense
-                # cubes (origin_amd/sparse.py): indices are those of the EXTENDED tile, entries
-                # outside res["box"] / not owned belong to the neighbours
-                from . import sparse
-                if crop:
-                    raise ValueError("local_max='sparse' goes with correl=None (no crop at all)")
-                if int(size) != 3 or sparse.plan(ctx, self.eshape)[0] == 0:
-                    raise ValueError("no sparse local-maximum form for this tile (size 3, Nx % 4)")
-                if getattr(self, "_lm_sparse", None) is None:
-                    self._lm_sparse = sparse.SparseBuffers(ctx, self.eshape)
-                res["local_max"], res["local_min"] = sparse.local_max_sparse(
-                    ctx, o["correl"], o["correl_min"], self.emask if mask is not None else None,
-                    self._lm_sparse)
-                return res
-            if self._lm is None:
-                self._lm = (ctx.empty(self.eshape, np.float32), ctx.empty(self.eshape, np.float32))
-            kernels.local_max(ctx, o["correl"], o["correl_min"],
-                              self.emask if mask is not None else None, size,
-                              out_max=self._lm[0], out_min=self._lm[1])
-            if local_max is True:   # no crop: the extended cubes (valid inside res["box"])
-                if crop:
-                    raise ValueError("local_max=True goes with correl=None (no crop at all)")
-                res["local_max"], res["local_min"] = self._lm
-            else:
-                for src, dst in zip(self._lm, local_max):
-                    _copy_box(ctx, dst, dst.shape, (0, 0, 0), src, self.eshape, (0, top, left),
-                              (Nz, ny, nx))
-                res["local_max"], res["local_min"] = local_max
-        return res
+            copy_box(ctx, self.maps[name], (1, ny, nx), (0, 0, 0), o[name], (1,) + self.eshape[1:],
+                     (0, top, left), (1, ny, nx))
+        return dict(correl=correl, profile=profile, correl_min=correl_min,
+                    maxmap=self.maps["maxmap"], minmap=self.maps["minmap"],
+                    box=(top, left, ny, nx) if not crop else (0, 0, ny, nx),
+                    # OwnerTiling: which spaxels of the box are this rank's (None: all of them)
+                    owned=self.tiling.owned_tile(self.rank))
+
+    def _local_maxima(self, o, emask, local_max, size):
+        """Stage 4: the local maxima of the extended GLR in the form ``run`` was asked for."""
+        ctx = self.ctx
+        if local_max == "sparse":
+            # (index, value) lists of the extended cubes' non-zero voxels instead of two dense
+            # cubes (origin_amd/sparse.py): indices are those of the EXTENDED tile, entries
+            # outside res["box"] / not owned belong to the neighbours
+            if self._lm_sparse is None:
+                self._lm_sparse = sparse.SparseBuffers(ctx, self.eshape)
+            return sparse.local_max_sparse(ctx, o["correl"], o["correl_min"], emask,
+                                           self._lm_sparse)
+        if self._lm is None:
+            self._lm = (ctx.empty(self.eshape, np.float32), ctx.empty(self.eshape, np.float32))
+        kernels.local_max(ctx, o["correl"], o["correl_min"], emask, size, out_max=self._lm[0],
+                          out_min=self._lm[1])
+        if local_max is True:   # no crop: the extended cubes (valid inside res["box"])
+            return self._lm
+        top, _, left, _ = self.halos
+        for src, dst in zip(self._lm, local_max):
+            copy_box(ctx, dst, dst.shape, (0, 0, 0), src, self.eshape, (0, top, left), self.shape)
+        return local_max

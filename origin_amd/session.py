@@ -36,7 +36,7 @@ import threading
 import numpy as np
 
 from . import _capi, kernels, multigpu, pipeline, sparse
-from .device import Context, DeviceArray
+from .device import Context, DeviceArray, copy_box
 from .pca import GreedyPCA
 
 
@@ -196,38 +196,39 @@ class TiledCube:
         self.group, self.shape, self.dtype, self.parts = group, tuple(shape), np.dtype(dtype), parts
         self.size = int(np.prod(self.shape))
 
-    def _gather(self, out, convert):
-        three = len(self.shape) == 3
+    def _part(self, rank):
+        """(a, crop, window, put) of part ``rank``: its array, the slices (by:by+ny, bx:bx+nx) of
+        its box in the array's last two axes, the slices (y0:y1, x0:x1) of the field window the
+        box covers, and ``put(dst, blk[, convert])``: the owned spaxels of the box-shaped ``blk``
+        into the window-shaped ``dst`` (last two axes)."""
+        a, (by, bx), (y0, y1, x0, x1), owned = self.parts[rank]
+        crop = (slice(by, by + y1 - y0), slice(bx, bx + x1 - x0))
 
+        def put(dst, blk, convert=lambda b: b):
+            if owned is None:
+                dst[...] = convert(blk)
+            else:
+                dst[..., owned] = convert(blk[..., owned])
+        return a, crop, (slice(y0, y1), slice(x0, x1)), put
+
+    def _gather(self, out, convert):
         def one(rank):
-            a, (by, bx), (y0, y1, x0, x1), owned = self.parts[rank]
-            ny, nx = y1 - y0, x1 - x0
-            if three:
+            a, crop, window, put = self._part(rank)
+            box = tuple(c.stop - c.start for c in crop)
+            # (sparse.SparseCube: zeros + its entries, on the host)
+            if hasattr(a, "entries") or len(self.shape) == 2 or a.shape[1:] == box:
+                blk = a.to_host()[(..., *crop)]
+            else:
                 # the part's box as one contiguous block: crop on the device (one strided copy
                 # kernel), then one large copy through pinned staging -- a strided device-to-host
                 # copy is one hipMemcpy2D per channel
-                if hasattr(a, "entries"):      # sparse.SparseCube: zeros + its entries, on the host
-                    blk = a.to_host()[:, by:by + ny, bx:bx + nx]
-                elif (by, bx) == (0, 0) and a.shape[1:] == (ny, nx):
-                    blk = a.to_host()
-                else:
-                    ctx = self.group.ctxs[rank]
-                    tmp = ctx.empty((a.shape[0], ny, nx), a.dtype)
-                    multigpu._copy_box(ctx, tmp, tmp.shape, (0, 0, 0), a, a.shape, (0, by, bx),
-                                       (a.shape[0], ny, nx))
-                    blk = tmp.to_host()
-                    tmp.free()
-                dst = out[:, y0:y1, x0:x1]
-                if owned is None:
-                    dst[...] = convert(blk)
-                else:
-                    dst[:, owned] = convert(blk[:, owned])
-            else:
-                blk = a.to_host()[by:by + ny, bx:bx + nx]
-                if owned is None:
-                    out[y0:y1, x0:x1] = convert(blk)
-                else:
-                    out[y0:y1, x0:x1][owned] = convert(blk[owned])
+                ctx = self.group.ctxs[rank]
+                tmp = ctx.empty((a.shape[0],) + box, a.dtype)
+                copy_box(ctx, tmp, tmp.shape, (0, 0, 0), a, a.shape, (0, crop[0].start,
+                                                                      crop[1].start), tmp.shape)
+                blk = tmp.to_host()
+                tmp.free()
+            put(out[(..., *window)], blk, convert)
         self.group.run(one)
         return out
 
@@ -248,12 +249,11 @@ class TiledCube:
     def _keep(self, rank, keep):
         """uint8 keep map over the spaxels of part ``rank``'s ARRAY: 1 where the spaxel is inside
         the part's box, owned, and kept by the caller's field map."""
-        a, (by, bx), (y0, y1, x0, x1), owned = self.parts[rank]
+        a, crop, window, put = self._part(rank)
         k = np.zeros(a.shape[1:], np.uint8)
-        w = np.ones((y1 - y0, x1 - x0), bool) if owned is None else owned.copy()
+        put(k[crop], np.ones_like(k[crop]))
         if keep is not None:
-            w &= np.asarray(keep).reshape(self.shape[1:])[y0:y1, x0:x1] != 0
-        k[by:by + y1 - y0, bx:bx + x1 - x0] = w
+            k[crop] &= np.asarray(keep).reshape(self.shape[1:])[window] != 0
         return k
 
     def zmax_map(self, keep=None):
@@ -262,16 +262,13 @@ class TiledCube:
         out = np.zeros(self.shape[1:], np.float64)
 
         def one(rank):
-            a, (by, bx), (y0, y1, x0, x1), owned = self.parts[rank]
+            a, crop, window, put = self._part(rank)
             ctx = self.group.ctxs[rank]
             full = a.zmax_map(None) if hasattr(a, "entries") else kernels.zmax_map(ctx, a, None)
-            m = full[by:by + y1 - y0, bx:bx + x1 - x0]
+            m = full[crop]
             if keep is not None:   # max_z (cube * keep) = keep ? max_z cube : 0
-                m = np.where(np.asarray(keep).reshape(self.shape[1:])[y0:y1, x0:x1] != 0, m, 0.0)
-            if owned is None:
-                out[y0:y1, x0:x1] = m
-            else:
-                out[y0:y1, x0:x1][owned] = m[owned]
+                m = np.where(np.asarray(keep).reshape(self.shape[1:])[window] != 0, m, 0.0)
+            put(out[window], m)
         self.group.run(one)
         return out
 
@@ -314,16 +311,15 @@ class TiledCube:
         """``np.where(cube > threshold)`` of the stitched cube, in NumPy's order, with the values
         (and those of the uint8 TiledCube ``aux`` with the same parts layout)."""
         def one(rank):
-            a, (by, bx), (y0, y1, x0, x1), owned = self.parts[rank]
+            a = self.parts[rank][0]
             ctx = self.group.ctxs[rank]
             ax = None if aux is None else aux.parts[rank][0]
             w = (a.where_above(threshold, aux=ax) if hasattr(a, "entries")
                  else kernels.where_above(ctx, a, threshold, aux=ax))
-            yy, xx = w["y"] - by, w["x"] - bx
-            ok = (yy >= 0) & (yy < y1 - y0) & (xx >= 0) & (xx < x1 - x0)
-            if owned is not None:
-                ok[ok] &= owned[yy[ok], xx[ok]]
-            res = dict(z=w["z"][ok], y=yy[ok] + y0, x=xx[ok] + x0, value=w["value"][ok])
+            ok = self._keep(rank, None)[w["y"], w["x"]] != 0
+            (by, bx), (y0, _, x0, _) = self.parts[rank][1:3]
+            res = dict(z=w["z"][ok], y=w["y"][ok] - by + y0, x=w["x"][ok] - bx + x0,
+                       value=w["value"][ok])
             if aux is not None:
                 res["aux"] = w["aux"][ok]
             return res
@@ -338,52 +334,11 @@ def redistribute(ctx, comm, src_tiling, dst_tiling, rank, src, dst, bufs):
     """Columns of a cube from one partition of the field to another: ``src`` is this rank's
     (Nz, ny, nx) array over its bounding box in ``src_tiling`` (its owned spaxels valid), ``dst``
     the array over its box in ``dst_tiling``; afterwards the spaxels this rank owns in
-    ``dst_tiling`` hold the cube's values, wherever they lived before.  Lists of spaxel columns
-    through the same gather / exchange / scatter as the halo of an ``OwnerTiling``."""
-    Nz = src.shape[0]
-    st, dt = src_tiling.tile(rank), dst_tiling.tile(rank)
-    s_nx, d_nx = st.x1 - st.x0, dt.x1 - dt.x0
-    mine_src = src_tiling.owner == rank
-    mine_dst = dst_tiling.owner == rank
-    es = src.dtype.itemsize
-    sends, recvs, local = [], [], None
-    for other in range(src_tiling.world):
-        ys, xs = np.nonzero(mine_src & (dst_tiling.owner == other))
-        if len(ys):
-            ix = ((ys - st.y0) * s_nx + (xs - st.x0)).astype(np.int32)
-            if other == rank:
-                local = [ix]
-            else:
-                sends.append((other, ix))
-        ys, xs = np.nonzero(mine_dst & (src_tiling.owner == other))
-        if len(ys):
-            ix = ((ys - dt.y0) * d_nx + (xs - dt.x0)).astype(np.int32)
-            if other == rank:
-                local.append(ix)
-            else:
-                recvs.append((other, ix))
-
-    def pack(ix):
-        d_ix = ctx.to_device(ix)
-        b = ctx.empty((Nz, ix.size), src.dtype)
-        _capi.call("origin_gather_columns", ctx.handle, src.p, Nz, src.size // Nz, d_ix.p, ix.size,
-                   es, b.p)
-        return b
-
-    def unpack(ix, b):
-        d_ix = ctx.to_device(ix)
-        _capi.call("origin_scatter_columns", ctx.handle, dst.p, Nz, dst.size // Nz, d_ix.p, ix.size,
-                   es, b.p)
-        bufs.append((d_ix, b))     # (alive until the stream has run the scatter)
-    if local is not None:
-        unpack(local[1], pack(local[0]))
-    out = [(peer, pack(ix)) for peer, ix in sends]
-    inn = [(peer, ctx.empty((Nz, ix.size), src.dtype)) for peer, ix in recvs]
-    comm.exchange(ctx, out, inn)
-    for (peer, ix), (_, b) in zip(recvs, inn):
-        unpack(ix, b)
-    bufs.extend(b for _, b in out)
-    return dst
+    ``dst_tiling`` hold the cube's values, wherever they lived before.  ``bufs``: a dict the
+    caller holds until the stream has run the last scatter (``ctx.sync()``): the index lists and
+    every buffer live in it, so none is freed before."""
+    return multigpu.exchange_pieces(ctx, comm, src, dst, ("plan", src_tiling, dst_tiling, rank),
+                                    lambda: multigpu.move_plan(src_tiling, dst_tiling, rank), bufs)
 
 
 # ------------------------------------------------------------------------------- session
@@ -399,23 +354,23 @@ class TiledSession:
         self.rk = [dict() for _ in range(self.world)]   # per-rank device state
 
     # -- helpers -------------------------------------------------------------------
-    def _cube(self, name, shape, dtype, tiling, halo_box=False):
+    def _cube(self, name, dtype, tiling, halo_box=False):
         """TiledCube over the per-rank arrays ``self.rk[r][name]``: tile-shaped (halo_box False) or
         extended-box-shaped."""
         parts = []
         for r in range(self.world):
             t = tiling.tile(r)
-            (_, _, _, _), (top, _, left, _) = tiling.extended(r)
+            top, _, left, _ = tiling.extended(r)[1]
             parts.append((self.rk[r][name], (top, left) if halo_box else (0, 0),
                           (t.y0, t.y1, t.x0, t.x1), tiling.owned_tile(r)))
-        return TiledCube(self.group, shape, dtype, parts)
+        return TiledCube(self.group, self.shape, dtype, parts)
 
     def _stitch_image(self, tiling, tiles, dtype=np.float64):
         out = np.zeros((tiling.Ny, tiling.Nx), dtype)
         for r, img in enumerate(tiles):
             t = tiling.tile(r)
-            own = tiling.owned_tile(r)
-            out[t.y0:t.y1, t.x0:t.x1][own] = np.asarray(img).reshape(own.shape)[own]
+            own = Ellipsis if tiling.owned_tile(r) is None else tiling.owned_tile(r)
+            out[t.y0:t.y1, t.x0:t.x1][own] = np.asarray(img).reshape(tiling.tile_shape(r))[own]
         return out
 
     def distribute(self, host, tiling, name, dtype=np.float32):
@@ -456,12 +411,9 @@ class TiledSession:
             d_var = ctx.to_device(np.ascontiguousarray(var[sl]), np.float32)
             d_mask = ctx.to_device(np.ascontiguousarray(mask[sl]), np.uint8)
             st.update(raw=d_raw, var=d_var, mask=d_mask)
-            if comm.device_p2p:
-                pre = pipeline.preprocess(ctx, d_raw, d_var, d_mask, dct_order, dct_approx,
-                                          allreduce_dev=comm.allreduce_sum_device)
-            else:
-                pre = pipeline.preprocess(ctx, d_raw, d_var, d_mask, dct_order, dct_approx,
-                                          allreduce=comm.allreduce_sum)
+            how = (dict(allreduce_dev=comm.allreduce_sum_device) if comm.device_p2p
+                   else dict(allreduce=comm.allreduce_sum))
+            pre = pipeline.preprocess(ctx, d_raw, d_var, d_mask, dct_order, dct_approx, **how)
             st.update(cube_std=pre["cube_std"], cont_dct=pre["cont_dct"])
             # 3x3x3 local maxima of cube_std (steps.py:453): one spaxel of halo, cube and mask
             strips = {}
@@ -475,10 +427,10 @@ class TiledSession:
                         o2=pre["o2_host"], cont_o2=cont_o2)
         res = self.group.run(one)
         out = {k: self._stitch_image(p1, [x[k] for x in res]) for k in res[0]}
-        out["cube_std"] = self._cube("cube_std", self.shape, np.float32, p1)
-        out["cont_dct"] = self._cube("cont_dct", self.shape, np.float32, p1)
-        out["cube_std_local_max"] = self._cube("std_lmax", self.shape, np.float32, p1, True)
-        out["cube_std_local_min"] = self._cube("std_lmin", self.shape, np.float32, p1, True)
+        out["cube_std"] = self._cube("cube_std", np.float32, p1)
+        out["cont_dct"] = self._cube("cont_dct", np.float32, p1)
+        out["cube_std_local_max"] = self._cube("std_lmax", np.float32, p1, True)
+        out["cube_std_local_min"] = self._cube("std_lmin", np.float32, p1, True)
         return out
 
     # -- step 4 --------------------------------------------------------------------
@@ -515,32 +467,30 @@ class TiledSession:
         def one(r):
             ctx, comm, st = self.group.ctxs[r], self.group.comms[r], self.rk[r]
             t = p2.tile(r)
-            ny, nx = t.y1 - t.y0, t.x1 - t.x0
-            keep = []
+            keep = {}     # (the move's lists and buffers: alive until the ctx.sync() below)
             std2 = st.get("std2")
             if std2 is None:
-                std2 = st["std2"] = ctx.zeros((Nz, ny, nx), np.float32)
+                std2 = st["std2"] = ctx.zeros((Nz,) + p2.tile_shape(r), np.float32)
             redistribute(ctx, comm, p1, p2, r, st["cube_std"], std2, keep)
             owned = p2.owned_tile(r)
             amap = np.where(owned, areamap[t.y0:t.y1, t.x0:t.x1], 0)
             labels = np.unique(amap[amap > 0])
             lmap = np.where(amap > 0, np.searchsorted(labels, amap) + 1, 0)
             spx = pipeline.area_lists(lmap, len(labels))
-            (ey0, ey1, ex0, ex1), (top, _, left, _) = p2.extended(r)
+            e_shape, (top, _, left, _) = p2.ext_shape(r)
             ext = st.get("ext")
             if ext is None:
-                ext = st["ext"] = ctx.zeros((Nz, ey1 - ey0, ex1 - ex0), np.float32)
+                ext = st["ext"] = ctx.zeros((Nz,) + e_shape, np.float32)
             drv = st.setdefault("pca", GreedyPCA(ctx))
             _, mapO2, nstop, _ = pipeline.greedy_pca(
                 ctx, std2, lmap, len(labels), [thresholds[l - 1] for l in labels],
                 [testO2[l - 1] for l in labels], Noise_population, itermax, spx=spx, driver=drv,
                 into=(ext, top, left))
             ctx.sync()
-            del keep
             return mapO2, nstop
         res = self.group.run(one)
         mapO2 = self._stitch_image(p2, [m for m, _ in res])
-        faint = self._cube("ext", self.shape, np.float32, p2, True)
+        faint = self._cube("ext", np.float32, p2, True)
         return faint, mapO2, int(sum(n for _, n in res))
 
     # -- step 5 --------------------------------------------------------------------
@@ -563,8 +513,7 @@ class TiledSession:
 
         def one(r):
             ctx, comm, st = self.group.ctxs[r], self.group.comms[r], self.rk[r]
-            (ey0, ey1, ex0, ex1), (top, _, left, _) = p2.extended(r)
-            t = p2.tile(r)
+            ey0, ey1, ex0, ex1 = p2.extended(r)[0]
             if not mine:
                 st["ext"] = ctx.to_device(np.ascontiguousarray(host[:, ey0:ey1, ex0:ex1]),
                                           np.float32)
@@ -587,11 +536,9 @@ class TiledSession:
         res = self.group.run(one)
         out = dict(maxmap=self._stitch_image(p2, [a for a, _ in res]),
                    minmap=self._stitch_image(p2, [b for _, b in res]))
-        for name, key, dt in (("correl", "correl", np.float32), ("correl_min", "correl_min",
-                                                                 np.float32),
-                              ("profile", "profile", np.uint8), ("local_max", "lmax", np.float32),
-                              ("local_min", "lmin", np.float32)):
-            out[name] = self._cube(key, self.shape, dt, p2, True)
+        for name, key in (("correl", "correl"), ("correl_min", "correl_min"),
+                          ("profile", "profile"), ("local_max", "lmax"), ("local_min", "lmin")):
+            out[name] = self._cube(key, np.uint8 if key == "profile" else np.float32, p2, True)
         return out
 
     def close(self):

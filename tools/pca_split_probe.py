@@ -73,8 +73,8 @@ def main():
     for (y0, y1), c in (((0, h), ctx), ((h, N), ctx2)):
         ny = y1 - y0
         sub = ctx.empty((Nz, ny, N), np.float32)
-        from origin_amd.multigpu import _copy_box
-        _copy_box(ctx, sub, sub.shape, (0, 0, 0), std, std.shape, (0, y0, 0), (Nz, ny, N))
+        from origin_amd.device import copy_box
+        copy_box(ctx, sub, sub.shape, (0, 0, 0), std, std.shape, (0, y0, 0), (Nz, ny, N))
         am = amap[y0:y1]
         labels = np.unique(am)
         lm = np.searchsorted(labels, am) + 1
