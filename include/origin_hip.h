@@ -392,6 +392,16 @@ int origin_glr_plan_fold_eps(origin_glr_plan *plan, float *eps, int *active);
  * check bench.py's `executed` against the counter passes committed under profiles/. */
 int origin_glr_mfma_count_model(int num_cu, int terms, int K, int n_narrow, int Nz, int Ny, int Nx,
                                 int P, long *spatial, long *spectral);
+/* Which kernels the plan's next run takes, as the run itself decides it (read only; a weighted
+ * plan answers for the FOLD verdict it has now, which its first run measures): *spatial_mfma = 1
+ * if the spatial stage runs on the matrix cores; *spectral = the form of the spectral stage,
+ * 0 table, 1 normw, 2 norm_mfma (matrix cores), 3 packed, 4 fp32, 5 generic (fp32 FMA kernels,
+ * csrc/glr_fp32.hip); *lwt = the register-window half width of the packed form's tap rows (8, 16,
+ * 24, 29 or 32; 0: half widths above 32), *lwmax = the largest profile half width, *nborder = the
+ * spaxels within P/2 of the field's border (0 for a plan with a norm cube).  The tests use it to
+ * assert the kernel they were written for. */
+int origin_glr_plan_paths(origin_glr_plan *plan, int *spatial_mfma, int *spectral, int *lwt,
+                          int *lwmax, int *nborder);
 
 /* A GLR run in ROW BANDS: the same results as origin_glr_run, written band by band -- so that the
  * bands whose input is final can start while the greedy PCA still iterates over its last areas

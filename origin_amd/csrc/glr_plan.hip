@@ -638,6 +638,18 @@ int origin_glr_mfma_count_model(int num_cu, int terms, int K, int n_narrow, int 
   return ORIGIN_OK;
 }
 
+int origin_glr_plan_paths(origin_glr_plan *plan, int *spatial_mfma, int *spectral, int *lwt,
+                          int *lwmax, int *nborder) {
+  ORIGIN_CHECK_ARG(plan && spatial_mfma && spectral && lwt && lwmax && nborder, "null argument");
+  const GlrPaths paths = glr_paths(plan, glr_no_fold());
+  *spatial_mfma = paths.spatial_mfma ? 1 : 0;
+  *spectral = (int)paths.spectral;
+  *lwt = plan->lwt;
+  *lwmax = plan->lwmax;
+  *nborder = plan->nborder;
+  return ORIGIN_OK;
+}
+
 int origin_glr_plan_bytes(origin_glr_plan *plan, size_t *bytes) {
   ORIGIN_CHECK_ARG(plan && bytes, "null argument");
   *bytes = plan->bytes;

@@ -240,6 +240,19 @@ class GLRPlan:
         _capi.call("origin_glr_plan_fold_eps", self._h, C.byref(e), C.byref(a))
         return e.value, bool(a.value)
 
+    SPECTRAL_FORMS = ("table", "normw", "norm_mfma", "packed", "fp32", "generic")
+
+    def paths(self):
+        """Which kernels the next run takes (include/origin_hip.h origin_glr_plan_paths): a dict of
+        ``spatial_mfma`` (bool), ``spectral`` (one of SPECTRAL_FORMS: the first three run on the
+        matrix cores, the others are the fp32 FMA kernels of csrc/glr_fp32.hip), ``lwt`` (window
+        half width of the packed form), ``lwmax`` (largest profile half width) and ``nborder``
+        (spaxels of the packed form's border pass)."""
+        v = [C.c_int() for _ in range(5)]
+        _capi.call("origin_glr_plan_paths", self._h, *(C.byref(x) for x in v))
+        return dict(spatial_mfma=bool(v[0].value), spectral=self.SPECTRAL_FORMS[v[1].value],
+                    lwt=v[2].value, lwmax=v[3].value, nborder=v[4].value)
+
     def close(self):
         if self._h is not None and self._h.value:
             # (a plan outliving its context -- interpreter exit closes contexts first -- is not

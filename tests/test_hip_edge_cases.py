@@ -1,7 +1,13 @@
-"""GPU edge cases of the HIP path: ragged / odd sizes (which select the non-vectorised and
-unpacked kernel variants), PSF sizes without a specialised kernel, one profile, weights with
-the production PSF, degenerate PCA inputs, fully masked channels, and cross-checks between the
-table-normalised and the explicit-norm GLR paths.  Oracle: oracle/cpu_ref.py."""
+"""GPU edge cases of the HIP path: ragged / odd sizes, PSF sizes without a specialised kernel, one
+profile, weights with the production PSF, degenerate PCA inputs, fully masked channels, and
+cross-checks between the table-normalised and the explicit-norm GLR paths.  Oracle:
+oracle/cpu_ref.py.
+
+The GLR tests here give no precision, so they run the library default: both stages on the matrix
+cores ("f16x2": the table kernel, or the norm-cube forms of a weighted plan), and only the
+spatial stage of the 3 x 3 PSF on the fp32 kernels.  The fp32 FMA kernels (csrc/glr_fp32.hip:
+packed, unpacked and generic spectral forms, vectorised and non-vectorised spatial forms) are
+tested in tests/test_hip_glr_fp32.py."""
 import numpy as np
 import pytest
 
@@ -54,8 +60,10 @@ def test_glr_weights_production_psf(hip):
 
 
 def test_glr_table_path_equals_explicit_norm_path(hip):
-    """weights=None (border-class tables + packed kernels) vs one field with weights == 1
-    (explicit norm cube + generic kernels): same algebra, two code paths."""
+    """weights=None (border-class tables: the matrix-core table kernel) vs one field with
+    weights == 1 (explicit norm cube: the matrix-core norm forms): same algebra, two code paths.
+    Both runs take the default precision "f16x2"; the fp32 forms of the two paths are compared
+    with the oracle in tests/test_hip_glr_fp32.py."""
     Nz, Ny, Nx = 400, 64, 72
     cube = noise((Nz, Ny, Nx), 11)
     psf = synth.moffat_psf(Nz, 25).astype(float)
