@@ -360,7 +360,7 @@ int origin_glr_plan_destroy(origin_glr_plan *plan);
  * field, or a mosaic of weighted fields: per-field accumulation); the spectral
  * stage for profile half widths <= 32 and K <= 26 -- through the border-class table without
  * weight maps, through the plan's norm cube with them (that cube, [Nz + 96][Ny][Nx] float32, is
- * allocated and filled by the plan's first run): the FOLD form where the cube is smooth along z
+ * allocated with the plan and filled by its first run or by origin_glr_plan_prepare): the FOLD form where the cube is smooth along z
  * (origin_glr_plan_fold_eps; precision 1 or 2), else a second Toeplitz product (precision 1 only).
  * A stage that is not eligible runs the fp32 kernels; plans where neither stage is (a field
  * smaller than the PSF without weight maps, longer / more profiles) always report 0.  get
@@ -381,12 +381,20 @@ int origin_glr_plan_mfma_count(origin_glr_plan *plan, long *spatial, long *spect
  * maximum and the minimum (*active = 1): correl and correl_min carry a relative error <= eps, the
  * profile index is that of a maximum up to the same eps.
  * Plans with weight maps (an explicit norm cube): den_k[z, s] = norm[z, s] sum p_k^2 (1 + e)^2; eps
- * is measured by the plan's FIRST run on the norm cube it makes (+inf and inactive before), and
+ * is measured by the first run or by prepare (origin_glr_plan_prepare) on the norm cube either
+ * makes (+inf and inactive before), and
  * where it passes the stage is the same FOLD kernel with rsq(norm) of each voxel behind the loop
  * instead of a second Toeplitz product (the 32 channels at either end keep the two-product
  * kernel); bf16 plans included.
  * ORIGIN_GLR_NO_FOLD=1 in the environment runs the exact form everywhere. */
 int origin_glr_plan_fold_eps(origin_glr_plan *plan, float *eps, int *active);
+/* What a plan with weight maps (an explicit norm cube) owes before the form of its spectral stage is
+ * known, done now instead of inside its first run: the norm cube (PSFs and weight maps only), then
+ * eps of the FOLD form measured on it.  On the context's main stream; the eps read-back
+ * synchronises it, so call it where a wait is harmless -- never from a PCA tail hook.  Idempotent;
+ * nothing to do for plans without a norm cube.  origin_glr_run calls it itself; row bands and
+ * rectangles (origin_glr_run_rows) need it called first. */
+int origin_glr_plan_prepare(origin_ctx *ctx, origin_glr_plan *plan);
 /* The same arithmetic without a plan or a device (host only: num_cu compute units, `terms` = 3
  * for the f16 split, 1 for bf16; n_narrow = profiles of half width <= 16): lets the CPU tests
  * check bench.py's `executed` against the counter passes committed under profiles/. */
@@ -411,9 +419,14 @@ int origin_glr_plan_paths(origin_glr_plan *plan, int *spatial_mfma, int *spectra
  * stream), ORIGIN_GLR_SIDE to enqueue the band on the context's side stream (all compute units but
  * ORIGIN_GLR_SIDE_RESERVE, default an eighth of them; it starts behind everything the main stream was given before
  * the call).  origin_glr_run_finish makes the main stream wait for the side bands and writes the
- * maps (NULL: none).  Only plans whose two stages run the table kernels on the matrix cores
- * (one field, no weight maps, precision 1 or 2, odd PSF 5..41, profile half widths <= 32, K <= 26):
- * origin_glr_rows_supported; others return ORIGIN_E_STATE. */
+ * maps (NULL: none).  Only plans whose two stages run on the matrix cores (precision 1 or 2, odd
+ * PSF 5..41, profile half widths <= 32, K <= 26): one field without weight maps (the table kernel),
+ * or a mosaic of weighted fields AFTER origin_glr_plan_prepare -- the FOLD form on the norm cube
+ * where its eps passes, the two-product kernel otherwise (precision 1); a band never makes the
+ * norm cube or measures eps (that synchronises the stream).  origin_glr_rows_supported tells: 0
+ * for a weighted plan that is not prepared, whose bf16 eps test failed or that runs the fp32
+ * kernels.  Others return ORIGIN_E_STATE (naming origin_glr_plan_prepare where that is what is
+ * missing). */
 #define ORIGIN_GLR_FIRST 1
 #define ORIGIN_GLR_SIDE 2
 int origin_glr_rows_supported(origin_glr_plan *plan, int *ok);

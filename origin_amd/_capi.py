@@ -90,6 +90,7 @@ SIGNATURES = {
     "origin_glr_plan_bytes": [vp, PP(sz)],
     "origin_glr_plan_mfma_count": [vp, PP(i64), PP(i64)],
     "origin_glr_plan_fold_eps": [vp, PP(C.c_float), PP(i32)],
+    "origin_glr_plan_prepare": [vp, vp],
     "origin_glr_plan_paths": [vp, PP(i32), PP(i32), PP(i32), PP(i32), PP(i32)],
     "origin_glr_mfma_count_model": [i32, i32, i32, i32, i32, i32, i32, i32, PP(i64), PP(i64)],
     "origin_glr_work_elems": [vp, PP(sz)],

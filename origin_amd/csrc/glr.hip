@@ -62,9 +62,10 @@ int zero_pads(origin_ctx *ctx, const origin_glr_plan *pl, float *d_work, const G
   return ORIGIN_OK;
 }
 
-// spatial stage over the whole field: cube_fsf, and in a weighted plan's first run its norm cube
+// spatial stage over the whole field (regions: the 64 x 64 regions ry0 .. / rx0 .. of the matrix-core
+// kernel, nry <= 0 = all): cube_fsf, the fields of a weighted mosaic accumulated one by one
 int run_spatial(origin_ctx *ctx, origin_glr_plan *pl, bool on_mfma, const float *d_cube, float *fsf,
-                float *norm) {
+                int ry0 = 0, int nry = 0, int rx0 = 0, int nrx = 0) {
   const int Nz = pl->Nz, Ny = pl->Ny, Nx = pl->Nx, P = pl->P;
   const size_t S = (size_t)Ny * Nx;
   for (int f = 0; f < pl->nfields; ++f) {
@@ -74,35 +75,60 @@ int run_spatial(origin_ctx *ctx, origin_glr_plan *pl, bool on_mfma, const float 
     // matrix cores, two-term f16 split (glr_spatial_mfma.hip); weighted fields accumulate
     int rc = on_mfma
                  ? origin_spatial_mfma_launch(ctx, pl->precision == 2 ? 1 : 3, d_cube, wf, kf, Nz,
-                                              Ny, Nx, P, wf && f > 0, fsf)
+                                              Ny, Nx, P, wf && f > 0, fsf, ry0, nry, rx0, nrx)
                  : glr_fp32_spatial(ctx, d_cube, wf, kf, Nz, Ny, Nx, P, f > 0, fsf);
     if (rc) return rc;
-    if (pl->mode == 1 && !pl->normc_ready) {
-      const float *k2f = pl->d_k2 + (size_t)f * Nz * P * P;
-      if (int rc2 = glr_fp32_spatial(ctx, nullptr, wf, k2f, Nz, Ny, Nx, P, f > 0, norm)) return rc2;
-    }
   }
-  if (pl->mode == 1) pl->normc_ready = 1;
   return ORIGIN_OK;
 }
 
+// NORMW: rows of each partial map -- the table kernel's z chunks, then the 32-channel end tiles
+int normw_part_rows(const origin_ctx *ctx, const origin_glr_plan *pl) {
+  int zf0, zf1;
+  mf_fold_range(pl->Nz, &zf0, &zf1);
+  return origin_spectral_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx) + cdiv(zf0, 32) +
+         cdiv(pl->Nz - zf1, 32);
+}
+
 // NORMW: the FOLD form of the table kernel between the ends of the cube, the two-product kernel
-// for the 32 channels at either end; the partial maps of the ends follow those of the middle
-int run_spectral_normw(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectralIO *io) {
+// for the 32 channels at either end; the partial maps of the ends follow those of the middle.
+// rg: the spaxels of a band or rectangle (the rows of the partial maps are the whole field's)
+int run_spectral_normw(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectralIO *io,
+                       const NmRange &rg) {
   int zf0, zf1;
   mf_fold_range(pl->Nz, &zf0, &zf1);
   SpectralMfmaArgs a = glr_spectral_mfma_args(pl, io, true);
   a.rden = a.rdi_s = a.rden_fold = a.sden = nullptr;  // (no class tables: the norm cube instead)
   a.normc = io->norm;
-  a.part_rows = origin_spectral_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx) +
-                cdiv(zf0, 32) + cdiv(pl->Nz - zf1, 32);
+  a.part_rows = normw_part_rows(ctx, pl);
+  a.s_first = rg.s_first, a.s_count = rg.s_count, a.rx0 = rg.rx0, a.rx1 = rg.rx1;
   if (int rc = origin_spectral_mfma_launch(ctx, a)) return rc;
   int got = 0;
   int rc = origin_spectral_norm_mfma_launch_ends(
       ctx, io->fsf, io->norm, pl->d_atab, pl->d_atab2, pl->d_pwide, pl->K, pl->Nz, pl->Ny, pl->Nx,
-      io->mask, io->correl, io->profile, io->correl_min, io->pmax, io->pmin, zf0, zf1, io->nzc, &got);
+      io->mask, io->correl, io->profile, io->correl_min, io->pmax, io->pmin, zf0, zf1, io->nzc, &got,
+      rg);
   io->nzc += got;
   return rc;
+}
+
+// the matrix-core spectral stage of the plan's form over the spaxels of rg
+int run_spectral_mfma(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form, bool no_fold,
+                      GlrSpectralIO *io, const NmRange &rg) {
+  switch (form) {
+    case GLR_SPEC_NORMW:
+      return run_spectral_normw(ctx, pl, io, rg);
+    case GLR_SPEC_NORM_MFMA:
+      return origin_spectral_norm_mfma_launch(ctx, io->fsf, io->norm, pl->d_atab, pl->d_atab2,
+                                              pl->d_pwide, pl->K, pl->Nz, pl->Ny, pl->Nx, io->mask,
+                                              io->correl, io->profile, io->correl_min, io->part,
+                                              io->want_maps, &io->nzc, &io->pmax, &io->pmin, rg);
+    default: {
+      SpectralMfmaArgs a = glr_spectral_mfma_args(pl, io, !no_fold);
+      a.s_first = rg.s_first, a.s_count = rg.s_count, a.rx0 = rg.rx0, a.rx1 = rg.rx1;
+      return origin_spectral_mfma_launch(ctx, a);
+    }
+  }
 }
 
 }  // namespace
@@ -131,22 +157,29 @@ int origin_glr_run_rows(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cub
                              y1, 0, pl ? pl->Nx : 0, flags);
 }
 
-// ---- a GLR run in row bands (plans whose two stages run the table kernels on the matrix cores)
+// ---- a GLR run in row bands (plans whose two stages run on the matrix cores; a plan with a norm
+// cube after origin_glr_plan_prepare: the band makes neither the cube nor its eps)
 int origin_glr_run_rect(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cube,
                         const uint8_t *d_mask, float *d_work, float *d_correl, uint8_t *d_profile,
                         float *d_correl_min, int y0, int y1, int x0, int x1, int flags) {
   ORIGIN_USE(ctx);
   ORIGIN_CHECK_ARG(pl && pl->ctx == ctx, "plan does not belong to this context");
   ORIGIN_CHECK_ARG(d_cube && d_work && d_correl && d_profile && d_correl_min, "null pointer");
-  const int Nz = pl->Nz, Ny = pl->Ny, Nx = pl->Nx, P = pl->P;
+  const int Ny = pl->Ny, Nx = pl->Nx;
   ORIGIN_CHECK_ARG(y0 >= 0 && y0 < y1 && y1 <= Ny && y0 % 64 == 0 && (y1 % 64 == 0 || y1 == Ny),
                    "row band must start at a multiple of 64 and end at one or at Ny");
   ORIGIN_CHECK_ARG(x0 >= 0 && x0 < x1 && x1 <= Nx && x0 % 64 == 0 && (x1 % 64 == 0 || x1 == Nx),
                    "column range must start at a multiple of 64 and end at one or at Nx");
   const bool whole_rows = x0 == 0 && x1 == Nx;  // (then the waves are those of a run over the field)
   const bool no_fold = glr_no_fold();
-  if (!glr_paths(pl, no_fold).rows_ok()) {
-    origin_set_error("origin_glr_run_rows: the plan's stages do not run the matrix-core table kernels");
+  const GlrPaths paths = glr_paths(pl, no_fold);
+  if (!paths.prepared) {
+    origin_set_error("origin_glr_run_rows: a plan with a norm cube runs in bands after "
+                     "origin_glr_plan_prepare");
+    return ORIGIN_E_STATE;
+  }
+  if (!paths.rows_ok()) {
+    origin_set_error("origin_glr_run_rows: the plan's stages do not run the matrix-core kernels");
     return ORIGIN_E_STATE;
   }
   const GlrWork work(pl, d_work);
@@ -158,20 +191,16 @@ int origin_glr_run_rect(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cub
     if (int rc = origin_fork_begin(ctx, ctx->side, origin_make_side_stream)) return rc;
     std::swap(ctx->stream, ctx->side.stream);
   }
-  int rc = ORIGIN_OK;
-  {
-    ProfScope ps(ctx, K_GLR_SPATIAL);
-    rc = origin_spatial_mfma_launch(ctx, pl->precision == 2 ? 1 : 3, d_cube, nullptr, pl->d_k, Nz, Ny,
-                                    Nx, P, 0, work.fsf, y0 / 64, cdiv(y1 - y0, 64), x0 / 64,
-                                    cdiv(x1 - x0, 64));
-  }
+  int rc = run_spatial(ctx, pl, true, d_cube, work.fsf, y0 / 64, cdiv(y1 - y0, 64), x0 / 64,
+                       cdiv(x1 - x0, 64));
   if (rc == ORIGIN_OK) {
     ProfScope ps(ctx, K_GLR_SPECTRAL);
-    GlrSpectralIO io = {work.fsf, nullptr, d_mask, d_correl, d_profile, d_correl_min, work.part, true};
-    SpectralMfmaArgs a = glr_spectral_mfma_args(pl, &io, !no_fold);
-    a.s_first = (long)y0 * Nx, a.s_count = (long)(y1 - y0) * Nx;
-    if (!whole_rows) a.rx0 = x0, a.rx1 = x1;
-    rc = origin_spectral_mfma_launch(ctx, a);
+    const float *norm = pl->mode == 1 ? pl->d_normc + (size_t)MF_PAD_FRONT * Ny * Nx : nullptr;
+    GlrSpectralIO io = {work.fsf, norm, d_mask, d_correl, d_profile, d_correl_min, work.part, true};
+    NmRange rg;
+    rg.s_first = (long)y0 * Nx, rg.s_count = (long)(y1 - y0) * Nx;
+    if (!whole_rows) rg.rx0 = x0, rg.rx1 = x1;
+    rc = run_spectral_mfma(ctx, pl, paths.spectral, no_fold, &io, rg);
   }
   if (side) {
     std::swap(ctx->stream, ctx->side.stream);
@@ -188,7 +217,17 @@ int origin_glr_run_finish(origin_ctx *ctx, origin_glr_plan *pl, float *d_work, f
   if (!d_maxmap && !d_minmap) return ORIGIN_OK;
   const long S = (long)pl->Ny * pl->Nx;
   GlrSpectralIO io = {};
-  io.nzc = origin_spectral_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx);
+  // the rows of each partial map: those of the form the bands ran
+  switch (glr_paths(pl, glr_no_fold()).spectral) {
+    case GLR_SPEC_NORMW:
+      io.nzc = normw_part_rows(ctx, pl);
+      break;
+    case GLR_SPEC_NORM_MFMA:
+      io.nzc = origin_spectral_norm_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx);
+      break;
+    default:
+      io.nzc = origin_spectral_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx);
+  }
   io.pmax = GlrWork(pl, d_work).part;
   io.pmin = io.pmax + (size_t)io.nzc * S;
   ProfScope ps(ctx, K_SMALL);
@@ -205,39 +244,23 @@ int origin_glr_run(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cube,
   const long S = (long)pl->Ny * pl->Nx;
   const bool no_fold = glr_no_fold();
   const GlrWork work(pl, d_work);
-  // mode 1: norm_fsf depends on the PSFs and the weight maps only -- the first run computes it
-  // into the cube the plan keeps (padded like cube_fsf)
-  float *norm = pl->mode == 1 ? pl->d_normc + (size_t)MF_PAD_FRONT * S : nullptr;
-  if (int rc = zero_pads(ctx, pl, d_work, work)) return rc;
-
-  if (int rc = run_spatial(ctx, pl, glr_paths(pl, no_fold).spatial_mfma, d_cube, work.fsf, norm)) return rc;
-  // NORMW: the first run measures eps of the FOLD form on the norm cube it has just made
-  if (pl->mode == 1 && !pl->normw_checked && pl->d_atab_fold)
-    if (int rc = glr_plan_measure_normw_eps(ctx, pl, norm)) return rc;
-
-  // ---- spectral stage (asked now: the eps just measured decides between NORMW and two products)
+  // a plan with a norm cube: its first run makes the cube and measures eps of the FOLD form on it
+  // (nothing once origin_glr_plan_prepare or an earlier run has)
+  if (int rc = glr_plan_prepare(ctx, pl)) return rc;
+  const float *norm = pl->mode == 1 ? pl->d_normc + (size_t)MF_PAD_FRONT * S : nullptr;
+  // (asked now: the eps just measured decides between NORMW and two products)
   const GlrPaths paths = glr_paths(pl, no_fold);
+  if (int rc = zero_pads(ctx, pl, d_work, work)) return rc;
+  if (int rc = run_spatial(ctx, pl, paths.spatial_mfma, d_cube, work.fsf)) return rc;
+
+  // ---- spectral stage
   GlrSpectralIO io = {work.fsf, norm, d_mask, d_correl, d_profile, d_correl_min, work.part,
                       d_maxmap || d_minmap};
   {
     ProfScope ps(ctx, K_GLR_SPECTRAL);
-    int rc;
-    switch (paths.spectral) {
-      case GLR_SPEC_NORMW:
-        rc = run_spectral_normw(ctx, pl, &io);
-        break;
-      case GLR_SPEC_NORM_MFMA:
-        rc = origin_spectral_norm_mfma_launch(ctx, io.fsf, norm, pl->d_atab, pl->d_atab2, pl->d_pwide,
-                                              pl->K, pl->Nz, pl->Ny, pl->Nx, d_mask, d_correl,
-                                              d_profile, d_correl_min, io.part, io.want_maps,
-                                              &io.nzc, &io.pmax, &io.pmin);
-        break;
-      case GLR_SPEC_TABLE:
-        rc = origin_spectral_mfma_launch(ctx, glr_spectral_mfma_args(pl, &io, !no_fold));
-        break;
-      default:
-        rc = glr_fp32_spectral(ctx, pl, paths.spectral, &io, &ps);
-    }
+    int rc = paths.spectral_mfma()
+                 ? run_spectral_mfma(ctx, pl, paths.spectral, no_fold, &io, NmRange())
+                 : glr_fp32_spectral(ctx, pl, paths.spectral, &io, &ps);
     if (rc) return rc;
   }
   if (!io.want_maps) return ORIGIN_OK;

@@ -43,13 +43,13 @@ struct origin_glr_plan {
   uint4 *d_atab_fold = nullptr, *d_atab_bf16_fold = nullptr;
   float *d_rden_fold = nullptr, *d_sden = nullptr;
   float fold_eps = INFINITY;
-  // mode 1 (explicit norm cube): 1 once the first run has measured eps on the norm cube (then
+  // mode 1 (explicit norm cube): 1 once glr_plan_prepare has measured eps on the norm cube (then
   // fold_eps holds it) -- NORMW runs where it is <= MF_FOLD_EPS
   int normw_checked = 0;
   std::vector<int> h_order;  // processing order on the host (empty: no matrix-core tap tables)
   int precision = 0;  // 0 = fp32 FMA kernels, 1 = split-f16 MFMA stages, 2 = bf16 MFMA stages
   float *d_normc = nullptr;  // mode 1: norm_fsf [Nz][Ny][Nx], a constant of the plan (PSFs and weight
-                             // maps only): allocated with the plan, computed by the first run and kept
+                             // maps only): allocated with the plan, computed by glr_plan_prepare and kept
   int normc_ready = 0;
   size_t bytes = 0;
 };
@@ -66,9 +66,11 @@ enum GlrSpectral {
 struct GlrPaths {
   bool spatial_mfma;  // the spatial stage runs on the matrix cores
   GlrSpectral spectral;
+  bool prepared;  // no norm cube, or the plan has made it and measured its eps (glr_plan_prepare)
   bool spectral_mfma() const { return spectral <= GLR_SPEC_NORM_MFMA; }
-  // runs in row bands / rectangles: both stages on the table kernels of the matrix cores
-  bool rows_ok() const { return spatial_mfma && spectral == GLR_SPEC_TABLE; }
+  // runs in row bands / rectangles: both stages on the matrix cores, and whatever the spectral
+  // stage reads besides cube_fsf exists before the first band
+  bool rows_ok() const { return prepared && spatial_mfma && spectral_mfma(); }
 };
 // ORIGIN_GLR_NO_FOLD=1: the exact form everywhere (read per call: tests set it within a process)
 inline bool glr_no_fold() { return getenv("ORIGIN_GLR_NO_FOLD") != nullptr; }
@@ -93,8 +95,10 @@ struct GlrWork {
   }
 };
 
-// glr_plan.hip: eps of the FOLD form on the norm cube a weighted plan's first run has just made
-int glr_plan_measure_normw_eps(origin_ctx *ctx, origin_glr_plan *pl, const float *norm);
+// glr_plan.hip: what a plan with a norm cube owes before its spectral form is known -- the norm
+// cube, then eps of the FOLD form on it -- on the main stream (the eps read-back synchronises it);
+// once per plan, nothing for the others.  origin_glr_plan_prepare and origin_glr_run.
+int glr_plan_prepare(origin_ctx *ctx, origin_glr_plan *pl);
 
 // ---- glr_fp32.hip: the fp32 FMA kernels
 // out (+)= corr2(A * B, taps) per channel; A == NULL: the norm of the weights B
@@ -148,17 +152,25 @@ long origin_spectral_mfma_count(int num_cu, int terms, int K, int n_narrow, int 
 int origin_spectral_mfma_chunks(int num_cu, int Nz, int Ny, int Nx);
 
 // ---- glr_spectral_norm_mfma.hip: the same stage for plans with an explicit norm cube
+// the spaxels of a launch, as in SpectralMfmaArgs: a range (s_count > 0, s_first a multiple of 32),
+// a rectangle (rx1 > 0: columns rx0 .. rx1 - 1 of the range's rows), or neither: the whole field
+struct NmRange {
+  long s_first = 0, s_count = 0;
+  int rx0 = 0, rx1 = 0;
+};
 int origin_spectral_norm_mfma_max_k();
+// z chunks (rows of each partial map) of a launch over all channels, whatever spaxels it takes
+int origin_spectral_norm_mfma_chunks(int num_cu, int Nz, int Ny, int Nx);
 int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const float *norm,
                                      const uint4 *atab, const uint4 *atab2, const int *pinfo, int K,
                                      int Nz, int Ny, int Nx, const uint8_t *mask, float *correl,
                                      uint8_t *profile, float *correl_min, float *part,
                                      bool want_maps, int *nzc_out, float **pmax_out,
-                                     float **pmin_out);
+                                     float **pmin_out, const NmRange &rg);
 // the end tiles [0, zf0) and [zf1, Nz) of a plan whose other channels run NORMW
 int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const float *fsf, const float *norm,
                                           const uint4 *atab, const uint4 *atab2, const int *pinfo,
                                           int K, int Nz, int Ny, int Nx, const uint8_t *mask,
                                           float *correl, uint8_t *profile, float *correl_min,
                                           float *pmax, float *pmin, int zf0, int zf1, int prow0,
-                                          int *rows_out);
+                                          int *rows_out, const NmRange &rg);

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void norm_classes_kernel(const float *__restri
 // norm = 0 and den = 0 in both forms.  norm: channel 0 of the padded cube.  A thread takes
 // NE_ZT consecutive channels of one spaxel (their common window in registers), the squared taps
 // sit in LDS as dense 65-slot rows (slot u = channel offset u - 32); float bits through atomicMax
-// (values >= 0).  Runs once per plan, in its first run: ~0.1 s at 3681 x 600 x 600.
+// (values >= 0).  Runs once per plan (glr_plan_prepare): ~0.1 s at 3681 x 600 x 600.
 constexpr int NE_ZT = 4;
 __global__ __launch_bounds__(256) void normw_eps_kernel(const float *__restrict__ norm,
                                                         const float *__restrict__ taps2,
@@ -385,7 +385,8 @@ int build_mfma_tap_tables(origin_glr_plan *pl, const Profiles &prof, std::vector
 
 // the norm cube of a weighted plan (padded like cube_fsf: MF_PAD_FRONT zero channels in front,
 // MF_PAD_BACK behind) is a constant of the plan: allocated HERE, where the callers' memory
-// checks run and plan->bytes is read, and filled by the first run
+// checks run and plan->bytes is read, and filled by glr_plan_prepare (the first run, or
+// origin_glr_plan_prepare ahead of it)
 int alloc_norm_cube(origin_glr_plan *pl) {
   const size_t padded =
       ((size_t)pl->Nz + MF_PAD_FRONT + MF_PAD_BACK) * (size_t)pl->Ny * pl->Nx * sizeof(float);
@@ -474,6 +475,7 @@ int build_fold_tables(origin_glr_plan *pl, const std::vector<double> &fold_a) {
 
 GlrPaths glr_paths_at(const origin_glr_plan *pl, int precision, bool no_fold) {
   GlrPaths p;
+  p.prepared = pl->mode == 0 || (pl->normc_ready && pl->normw_checked);
   // the matrix-core stages need the plan's tap tables (weights=None) or its weight maps (a norm
   // cube without weight maps -- a field smaller than the PSF -- stays on the fp32 kernels)
   const bool mc = precision >= 1 && (pl->mode == 0 ? pl->d_atab != nullptr : pl->d_w != nullptr);
@@ -499,7 +501,8 @@ GlrPaths glr_paths_at(const origin_glr_plan *pl, int precision, bool no_fold) {
   return p;
 }
 
-int glr_plan_measure_normw_eps(origin_ctx *ctx, origin_glr_plan *pl, const float *norm) {
+// eps of the FOLD form on the norm cube (channel 0 at norm) the plan has just made
+static int measure_normw_eps(origin_ctx *ctx, origin_glr_plan *pl, const float *norm) {
   pl->normw_checked = 1;
   pl->fold_eps = INFINITY;
   int zf0, zf1;
@@ -520,7 +523,38 @@ int glr_plan_measure_normw_eps(origin_ctx *ctx, origin_glr_plan *pl, const float
   return ORIGIN_OK;
 }
 
+int glr_plan_prepare(origin_ctx *ctx, origin_glr_plan *pl) {
+  if (pl->mode != 1) return ORIGIN_OK;
+  const int Nz = pl->Nz, Ny = pl->Ny, Nx = pl->Nx, P = pl->P;
+  const size_t S = (size_t)Ny * Nx;
+  float *norm = pl->d_normc + (size_t)MF_PAD_FRONT * S;
+  if (!pl->normc_ready) {
+    // norm_fsf depends on the PSFs and the weight maps only: made once, into the cube the plan
+    // keeps (padded like cube_fsf; alloc_norm_cube zeroed the pads)
+    ProfScope ps(ctx, K_GLR_SPATIAL);
+    for (int f = 0; f < pl->nfields; ++f) {
+      const float *wf = pl->d_w ? pl->d_w + (size_t)f * S : nullptr;
+      const float *k2f = pl->d_k2 + (size_t)f * Nz * P * P;
+      if (int rc = glr_fp32_spatial(ctx, nullptr, wf, k2f, Nz, Ny, Nx, P, f > 0, norm)) return rc;
+    }
+    pl->normc_ready = 1;
+  }
+  // NORMW: eps of the FOLD form, measured on that cube (plans without folded taps run the exact
+  // forms whatever it would be)
+  if (!pl->normw_checked) {
+    if (pl->d_atab_fold) return measure_normw_eps(ctx, pl, norm);
+    pl->normw_checked = 1;
+  }
+  return ORIGIN_OK;
+}
+
 extern "C" {
+
+int origin_glr_plan_prepare(origin_ctx *ctx, origin_glr_plan *plan) {
+  ORIGIN_USE(ctx);
+  ORIGIN_CHECK_ARG(plan && plan->ctx == ctx, "plan does not belong to this context");
+  return glr_plan_prepare(ctx, plan);
+}
 
 int origin_glr_plan_destroy(origin_glr_plan *plan) {
   if (!plan) return ORIGIN_OK;
@@ -602,8 +636,8 @@ int origin_glr_plan_get_precision(origin_glr_plan *plan, int *precision) {
 int origin_glr_plan_fold_eps(origin_glr_plan *plan, float *eps, int *active) {
   ORIGIN_CHECK_ARG(plan && eps && active, "null argument");
   *eps = plan->fold_eps;
-  // (a plan with a norm cube measures eps in its first run: +inf and inactive before that.
-  // `active` is the verdict of the eps test, not the form that runs: glr_paths keeps a plan whose
+  // (a plan with a norm cube measures eps in its first run or in origin_glr_plan_prepare: +inf
+  // and inactive before that.  `active` is the verdict of the eps test, not the form that runs: glr_paths keeps a plan whose
   // eps passes on the exact kernels when it has one profile pair only, or -- with a norm cube --
   // when the partial maps of NORMW's three launches would not fit their 64 rows)
   *active = (plan->mode == 0 ? plan->d_rden_fold != nullptr

@@ -21,19 +21,23 @@
 // belong to the last launch.
 //
 // Round 3: where the norm cube is smooth along z -- den_k[z, s] = norm[z, s] sum_j p_k[j]^2 up to
-// a relative eps the plan measures in its first run -- the table kernel's FOLD form takes over
+// a relative eps the plan measures once (glr_plan_prepare) -- the table kernel's FOLD form takes over
 // between the cube's ends (glr_spectral_mfma.hip, NORMW: one Toeplitz product, rsq(norm) of each
 // voxel behind the profile loop; 28.6 -> 10.4 ms for two fields at 3681 x 600 x 600) and this
 // kernel keeps the 32 channels at either end (origin_spectral_norm_mfma_launch_ends) and the plans
 // whose eps is too large.
+//
+// Like the table kernel a launch takes the whole field, a range of spaxels (a row band: the waves
+// hold the spaxels they hold in a launch over the field, so a run in bands is bit for bit the run)
+// or a rectangle of 64 x 64 regions (a wave holds 32 columns of one row); the z chunks and the
+// rows of the partial maps are those of the whole field whatever part a launch takes.
 //
 // This is the straightforward form: no software pipelining of the epilogue under the next pair's
 // MFMAs, the whole 96-channel window of both cubes converted per tile, two waves per SIMD.  It
 // replaces an fp32 kernel that took 110 ms for two fields at 3681 x 600 x 600.
 #include <algorithm>
 
-#include "common.h"
-#include "glr_tables.h"
+#include "glr_plan.h"
 
 namespace {
 
@@ -133,10 +137,16 @@ __global__ __launch_bounds__(64 * NW, 1) void spectral_norm_mfma_kernel(
     const uint4 *__restrict__ atab2, const int *__restrict__ pinfo, int K, int Nz, int Ny, int Nx,
     int zchunk, const uint8_t *__restrict__ mask, float *__restrict__ correl,
     uint8_t *__restrict__ profile, float *__restrict__ correl_min, float *__restrict__ part_max,
-    float *__restrict__ part_min, int zstart, int zstop, int prow0) {
+    float *__restrict__ part_min, int zstart, int zstop, int prow0, long s_first,
+    long s_end_launch, int rx0, int rx1) {
   // (zstart, zstop: the channels of this launch, chunk c = [zstart + c zchunk, ...); prow0: row of
   // the partial maps that chunk 0 writes -- the FOLD form of the table kernel leaves the 32
   // channels at either end of the cube to this kernel)
+  // (s_first, s_end_launch: the spaxels of this launch, s_first a multiple of 32 -- a run may be
+  // split into row bands; waves hold the same 32 spaxels as in a launch over the field.  rx1 > 0:
+  // a RECTANGLE instead -- the rows s_first / Nx .. s_end_launch / Nx, columns rx0 .. rx1 - 1 of
+  // each; a wave holds 32 consecutive columns of one row.  As in glr_spectral_mfma.hip; the
+  // partial maps keep the whole field's rows of S entries.)
   extern __shared__ __align__(16) char nm_lds[];
   {
     const int nvec = K * (MF_PROF_BYTES / 16);
@@ -150,16 +160,25 @@ __global__ __launch_bounds__(64 * NW, 1) void spectral_norm_mfma_kernel(
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const long s_base = ((long)blockIdx.x * NW + wv) * 32;
-  if (s_base >= S) return;  // whole wave; no barrier follows
+  const long w_col = (long)blockIdx.x * NW + wv;
+  long s_end = s_end_launch;
+  long s_base = s_first + w_col * 32;
+  if (rx1 > 0) {
+    const int wpr = (rx1 - rx0 + 31) / 32;  // waves per row
+    const long row = s_first / Nx + w_col / wpr;
+    if (row >= s_end / Nx) return;
+    s_base = row * Nx + rx0 + 32 * (int)(w_col % wpr);
+    s_end = row * Nx + rx1;
+  }
+  if (s_base >= s_end) return;  // whole wave; no barrier follows
   const int zc0 = zstart + blockIdx.y * zchunk, zc1 = min(zstop, zc0 + zchunk);
   const int E0 = 8 * h - (r & 15) + 31;
   const char *a_lane = nm_lds + (E0 & 7) * MF_COPY_BYTES + (E0 >> 3) * 16;
   const char *a2_lane = a_lane + K * MF_PROF_BYTES;
   const bool second = (lane & 16) != 0;  // this lane's A rows belong to the pair's profile b
-  const bool sv = s_base + r < S;
-  const bool all_valid = s_base + 32 <= S;
-  const long sc = sv ? s_base + r : S - 1;
+  const bool sv = s_base + r < s_end;
+  const bool all_valid = s_base + 32 <= s_end;
+  const long sc = sv ? s_base + r : s_end - 1;  // (lanes past the range hold a copy of its last)
   const int rr = (int)(sc - s_base);
   const int NP = (K + 1) / 2;
   float vmax = -INFINITY, vmin = INFINITY;
@@ -304,17 +323,42 @@ __global__ __launch_bounds__(64 * NW, 1) void spectral_norm_mfma_kernel(
 
 }  // namespace
 
+// the spaxels of a launch, as glr_spectral_mfma.hip takes them: s_count > 0: the range [s_first,
+// s_first + s_count), s_first a multiple of 32; rx1 > 0: columns rx0 .. rx1 - 1 of the range's
+// rows; neither: the whole field.  Fills the kernel's (s_first, s_end) and the blocks along x.
+static int nm_range(const NmRange &rg, int Ny, int Nx, long *s_first, long *s_end, long *bx) {
+  const long S = (long)Ny * Nx;
+  long s0 = rg.s_first, n = rg.s_count;
+  if (n <= 0) s0 = 0, n = S;
+  if ((rg.rx1 <= 0 && s0 % 32 != 0) || s0 < 0 || s0 + n > S) {
+    origin_set_error("spectral norm MFMA kernel: bad spaxel range");
+    return ORIGIN_E_ARG;
+  }
+  long ncols = cdiv(n, 32);  // columns (32 spaxels x one z chunk): one per wave
+  if (rg.rx1 > 0) {
+    if (s0 % Nx != 0 || n % Nx != 0 || rg.rx0 < 0 || rg.rx0 >= rg.rx1 || rg.rx1 > Nx) {
+      origin_set_error("spectral norm MFMA kernel: bad rectangle");
+      return ORIGIN_E_ARG;
+    }
+    ncols = (n / Nx) * (long)cdiv(rg.rx1 - rg.rx0, 32);
+  }
+  *s_first = s0, *s_end = s0 + n, *bx = cdiv(ncols, NW);
+  return ORIGIN_OK;
+}
+
 // the launches over the halves of the profile list for the channels [zstart, zstop) in chunks of
-// zcm (grid.y = nchunks); partial maps from row prow0 on
+// zcm (grid.y = nchunks) and the spaxels of rg; partial maps from row prow0 on
 static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const uint4 *atab,
                      const uint4 *atab2, const int *pinfo, int K, int Nz, int Ny, int Nx,
                      const uint8_t *mask, float *correl, uint8_t *profile, float *correl_min,
-                     float *pmax, float *pmin, long bx, int nchunks, int zcm, int zstart, int zstop,
-                     int prow0) {
+                     float *pmax, float *pmin, const NmRange &rg, int nchunks, int zcm, int zstart,
+                     int zstop, int prow0) {
   if (K > 2 * NM_MAX_K) {
     origin_set_error("spectral norm MFMA kernel: %d profiles (at most %d)", K, 2 * NM_MAX_K);
     return ORIGIN_E_ARG;
   }
+  long s_first, s_end, bx;
+  if (int rc = nm_range(rg, Ny, Nx, &s_first, &s_end, &bx)) return rc;
   const int npass = K > NM_MAX_K ? 2 : 1;
   const int K0 = npass == 2 ? (K / 2 + 1) / 2 * 2 : K;  // an even count first: whole pairs
   static OriginPerDeviceOnce attr_once;
@@ -326,7 +370,7 @@ static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const
                          ORIGIN_HIP(hipFuncSetAttribute(
                              (const void *)spectral_norm_mfma_kernel<true>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, dyn)));
-  for (int pass = 0; pass < npass; ++pass) {
+  for (int pass = 0; pass < npass; ++pass) {  // (both passes over the same spaxels)
     const int s0 = pass == 0 ? 0 : K0, Kl = pass == 0 ? K0 : K - K0;
     const bool last = pass == npass - 1;
     const size_t lds = (size_t)Kl * 2 * MF_PROF_BYTES;
@@ -338,11 +382,11 @@ static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const
     if (pass == 0)
       hipLaunchKernelGGL(spectral_norm_mfma_kernel<false>, grid, block, lds, ctx->stream, fsf, norm,
                          ta, tb, pinfo + s0, Kl, Nz, Ny, Nx, zcm, mk, correl, profile, correl_min,
-                         qmax, qmin, zstart, zstop, prow0);
+                         qmax, qmin, zstart, zstop, prow0, s_first, s_end, rg.rx0, rg.rx1);
     else
       hipLaunchKernelGGL(spectral_norm_mfma_kernel<true>, grid, block, lds, ctx->stream, fsf, norm,
                          ta, tb, pinfo + s0, Kl, Nz, Ny, Nx, zcm, mk, correl, profile, correl_min,
-                         qmax, qmin, zstart, zstop, prow0);
+                         qmax, qmin, zstart, zstop, prow0, s_first, s_end, rg.rx0, rg.rx1);
     ORIGIN_LAUNCH_CHECK();
   }
   return ORIGIN_OK;
@@ -350,18 +394,12 @@ static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const
 
 int origin_spectral_norm_mfma_max_k() { return 2 * NM_MAX_K; }
 
-// fsf and norm: cubes padded with MF_PAD_FRONT zero channels in front and MF_PAD_BACK behind (the
-// pointers are to channel 0).  atab / atab2: tap and tap^2 tables in processing order (glr.hip),
-// pinfo the profile of each slot.  Two launches over the halves of the profile list.
-int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const float *norm,
-                                     const uint4 *atab, const uint4 *atab2, const int *pinfo, int K,
-                                     int Nz, int Ny, int Nx, const uint8_t *mask, float *correl,
-                                     uint8_t *profile, float *correl_min, float *part,
-                                     bool want_maps, int *nzc_out, float **pmax_out,
-                                     float **pmin_out) {
-  const long S = (long)Ny * Nx;
+// z chunks of a launch over all channels: whole rounds of the chip for the blocks of the WHOLE
+// field, whatever part of it a launch takes -- the partial maps of all parts of a run share their
+// layout and a band's z tiles are the whole run's
+static void nm_geometry(int num_cu, int Nz, long S, int *nzm_out, int *zcm_out) {
   const long bx = cdiv(S, 32 * NW);
-  const int ncu = std::max(1, ctx->num_cu);
+  const int ncu = std::max(1, num_cu);
   int nzm = 1;
   double best_eff = 0.0;
   for (int n = 1; n <= std::min(64, std::max(1, cdiv(Nz, 64))); ++n) {
@@ -372,11 +410,32 @@ int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const fl
     if (eff > best_eff * 1.0001) best_eff = eff, nzm = n;
   }
   const int zcm = (cdiv(Nz, nzm) + 31) / 32 * 32;
-  nzm = cdiv(Nz, zcm);
+  *nzm_out = cdiv(Nz, zcm);
+  *zcm_out = zcm;
+}
+
+int origin_spectral_norm_mfma_chunks(int num_cu, int Nz, int Ny, int Nx) {
+  int nzm, zcm;
+  nm_geometry(num_cu, Nz, (long)Ny * Nx, &nzm, &zcm);
+  return nzm;
+}
+
+// fsf and norm: cubes padded with MF_PAD_FRONT zero channels in front and MF_PAD_BACK behind (the
+// pointers are to channel 0).  atab / atab2: tap and tap^2 tables in processing order (glr.hip),
+// pinfo the profile of each slot.  Two launches over the halves of the profile list.
+int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const float *norm,
+                                     const uint4 *atab, const uint4 *atab2, const int *pinfo, int K,
+                                     int Nz, int Ny, int Nx, const uint8_t *mask, float *correl,
+                                     uint8_t *profile, float *correl_min, float *part,
+                                     bool want_maps, int *nzc_out, float **pmax_out,
+                                     float **pmin_out, const NmRange &rg) {
+  const long S = (long)Ny * Nx;
+  int nzm, zcm;
+  nm_geometry(ctx->num_cu, Nz, S, &nzm, &zcm);
   float *pmax = want_maps ? part : nullptr;
   float *pmin = want_maps ? part + (size_t)nzm * S : nullptr;
   int rc = nm_passes(ctx, fsf, norm, atab, atab2, pinfo, K, Nz, Ny, Nx, mask, correl, profile,
-                     correl_min, pmax, pmin, bx, nzm, zcm, 0, Nz, 0);
+                     correl_min, pmax, pmin, rg, nzm, zcm, 0, Nz, 0);
   if (rc) return rc;
   *nzc_out = nzm;
   *pmax_out = pmax;
@@ -392,21 +451,19 @@ int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const float *fsf, con
                                           int K, int Nz, int Ny, int Nx, const uint8_t *mask,
                                           float *correl, uint8_t *profile, float *correl_min,
                                           float *pmax, float *pmin, int zf0, int zf1, int prow0,
-                                          int *rows_out) {
-  const long S = (long)Ny * Nx;
-  const long bx = cdiv(S, 32 * NW);
+                                          int *rows_out, const NmRange &rg) {
   int rows = 0;
   if (zf0 > 0) {
     const int n = cdiv(zf0, 32);
     int rc = nm_passes(ctx, fsf, norm, atab, atab2, pinfo, K, Nz, Ny, Nx, mask, correl, profile,
-                       correl_min, pmax, pmin, bx, n, 32, 0, zf0, prow0);
+                       correl_min, pmax, pmin, rg, n, 32, 0, zf0, prow0);
     if (rc) return rc;
     rows += n;
   }
   if (zf1 < Nz) {
     const int n = cdiv(Nz - zf1, 32);
     int rc = nm_passes(ctx, fsf, norm, atab, atab2, pinfo, K, Nz, Ny, Nx, mask, correl, profile,
-                       correl_min, pmax, pmin, bx, n, 32, zf1, Nz, prow0 + rows);
+                       correl_min, pmax, pmin, rg, n, 32, zf1, Nz, prow0 + rows);
     if (rc) return rc;
     rows += n;
   }

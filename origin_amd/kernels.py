@@ -187,10 +187,22 @@ class GLRPlan:
                           and max(self.tap_lengths) <= 65))
 
     # -- the same run in row bands (include/origin_hip.h origin_glr_run_rows) ---------------
+    def prepare(self):
+        """What a plan with weight maps owes before its spectral form is known, now instead of
+        inside its first ``run``: the norm cube, then eps of the FOLD form measured on it
+        (include/origin_hip.h origin_glr_plan_prepare).  On the main stream, which it
+        synchronises: call it ahead of the step, never from a PCA tail hook.  Idempotent; nothing
+        to do for a plan without weight maps.  Returns self."""
+        _capi.call("origin_glr_plan_prepare", self.ctx.handle, self._h)
+        return self
+
     def rows_supported(self):
-        """Whether the plan's two stages run the table kernels on the matrix cores (one field,
-        no weight maps, a PSF size of SPATIAL_MFMA_SIZES, half widths <= 32): only those plans
-        run in row bands."""
+        """Whether the plan runs in row bands and rectangles: both stages on the matrix cores (a
+        PSF size of SPATIAL_MFMA_SIZES, half widths <= 32, K <= 26) -- one field without weight
+        maps, or a mosaic of weighted fields once ``prepare()`` has made its norm cube and
+        measured eps (the FOLD form on the norm cube, or the two-product kernel at "f16x2").  A
+        weighted plan answers False before ``prepare()``, at "f32", and at "bf16" when its eps
+        test fails."""
         ok = C.c_int()
         _capi.call("origin_glr_rows_supported", self._h, C.byref(ok))
         return bool(ok.value)
@@ -199,7 +211,8 @@ class GLRPlan:
         """The rows [y0, y1) of a run (y0 a multiple of 64, y1 one or Ny): spatial stage (reads
         cube rows [y0 - P//2, y1 + P//2)), spectral stage, partial maps.  ``first``: the first band
         of a run; ``side``: enqueue on the context's side stream (all CUs but a reserve), behind
-        what the main stream holds now."""
+        what the main stream holds now.  A plan with weight maps accumulates its fields into the
+        band and reads its norm cube: ``prepare()`` first (the band raises otherwise)."""
         assert cube.shape == self.shape and cube.dtype == np.float32
         _capi.call("origin_glr_run_rows", self.ctx.handle, self._h, cube.p, _p(mask),
                    self.workspace().p, correl.p, profile.p, correl_min.p, int(y0), int(y1),
@@ -208,8 +221,9 @@ class GLRPlan:
     def run_rect(self, cube, mask, correl, profile, correl_min, y0, y1, x0, x1, first=False,
                  side=False):
         """Rows [y0, y1) x columns [x0, x1) of a run (each a multiple of 64 or the field's end);
-        see ``run_rows``.  With a proper column range the results agree with ``run`` to rounding
-        (the spectral stage's waves hold 32 columns of one row), not bit for bit."""
+        see ``run_rows`` (weighted plans included).  With a proper column range the results agree
+        with ``run`` to rounding (the spectral stage's waves hold 32 columns of one row), not bit
+        for bit."""
         assert cube.shape == self.shape and cube.dtype == np.float32
         _capi.call("origin_glr_run_rect", self.ctx.handle, self._h, cube.p, _p(mask),
                    self.workspace().p, correl.p, profile.p, correl_min.p, int(y0), int(y1), int(x0),

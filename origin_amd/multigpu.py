@@ -829,6 +829,14 @@ class TiledGLR:
     def _rects(self, regions):
         return region_rects(regions, self.eshape[1], self.eshape[2], R)
 
+    def _rects_supported(self):
+        """Whether the plan takes rectangles -- its final verdict: a plan of weighted fields makes
+        the norm cube of the extended tile and measures the eps of its FOLD form first (once; the
+        measurement synchronises the stream, so this is asked ahead of a step or of its tail hook,
+        never inside the hook)."""
+        self.plan.prepare()
+        return self.plan.rows_supported()
+
     def make_tail_hook(self, area_boxes, mask, early_budget=8.5e8):
         """A function for ``Context.set_pca_tail_hook`` around the greedy PCA that writes this
         tile (``into=faint_target()``): when few areas still iterate, the regions of the extended
@@ -838,7 +846,7 @@ class TiledGLR:
         coordinates, inclusive; ``early_budget``: voxels of GLR started that way at most.  The
         next ``run(None, ...)`` finishes the step."""
         self._set_mask(mask)   # (collective: here, on every rank, not inside the hook)
-        if not self.plan.rows_supported():
+        if not self._rects_supported():
             return None
 
         def hook(areas):
@@ -920,7 +928,7 @@ class TiledGLR:
         them; ORIGIN_TILED_INTERIOR_FIRST=0 leaves only what the hook started ahead."""
         interior = os.environ.get("ORIGIN_TILED_INTERIOR_FIRST", "1") != "0"
         rects = None
-        if cube_faint is None and self.plan.rows_supported() and (done is not None or interior):
+        if cube_faint is None and self._rects_supported() and (done is not None or interior):
             ahead, behind = self._split_regions(interior, done)
             rects = (self._rects(ahead), self._rects(behind))
             if not rects[0] and done is None:

@@ -200,6 +200,10 @@ def greedy_pca_then_glr(ctx, plan, cube_std, areamap, nbAreas, thresholds, testO
                           side=True)
         state["early"], state["late"] = early, late
 
+    # (a mosaic of weighted fields: its norm cube and the eps of its FOLD form now -- the
+    # measurement synchronises the stream, which the hook must not -- so that the verdict on bands
+    # is the final one)
+    plan.prepare()
     use = plan.rows_supported() and max_active > 0
     if use:
         ctx.set_pca_tail_hook(hook, max_active)
