@@ -62,10 +62,10 @@ int zero_pads(origin_ctx *ctx, const origin_glr_plan *pl, float *d_work, const G
   return ORIGIN_OK;
 }
 
-// spatial stage over the whole field (regions: the 64 x 64 regions ry0 .. / rx0 .. of the matrix-core
-// kernel, nry <= 0 = all): cube_fsf, the fields of a weighted mosaic accumulated one by one
+// spatial stage over the 64 x 64 regions that hold rg (the whole field on the fp32 kernel):
+// cube_fsf, the fields of a weighted mosaic accumulated one by one
 int run_spatial(origin_ctx *ctx, origin_glr_plan *pl, bool on_mfma, const float *d_cube, float *fsf,
-                int ry0 = 0, int nry = 0, int rx0 = 0, int nrx = 0) {
+                const GlrRange &rg) {
   const int Nz = pl->Nz, Ny = pl->Ny, Nx = pl->Nx, P = pl->P;
   const size_t S = (size_t)Ny * Nx;
   for (int f = 0; f < pl->nfields; ++f) {
@@ -73,67 +73,49 @@ int run_spatial(origin_ctx *ctx, origin_glr_plan *pl, bool on_mfma, const float 
     const float *kf = pl->d_k + (size_t)f * Nz * P * P;
     const float *wf = pl->d_w ? pl->d_w + (size_t)f * S : nullptr;
     // matrix cores, two-term f16 split (glr_spatial_mfma.hip); weighted fields accumulate
+    // (regions ry0, nry, rx0, nrx; none = all)
     int rc = on_mfma
                  ? origin_spatial_mfma_launch(ctx, pl->precision == 2 ? 1 : 3, d_cube, wf, kf, Nz,
-                                              Ny, Nx, P, wf && f > 0, fsf, ry0, nry, rx0, nrx)
+                                              Ny, Nx, P, wf && f > 0, fsf, rg.y0 / 64,
+                                              cdiv(rg.y1 - rg.y0, 64), rg.x0 / 64,
+                                              cdiv(rg.x1 - rg.x0, 64))
                  : glr_fp32_spatial(ctx, d_cube, wf, kf, Nz, Ny, Nx, P, f > 0, fsf);
     if (rc) return rc;
   }
   return ORIGIN_OK;
 }
 
-// NORMW: rows of each partial map -- the table kernel's z chunks, then the 32-channel end tiles
-int normw_part_rows(const origin_ctx *ctx, const origin_glr_plan *pl) {
-  int zf0, zf1;
-  mf_fold_range(pl->Nz, &zf0, &zf1);
-  return origin_spectral_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx) + cdiv(zf0, 32) +
-         cdiv(pl->Nz - zf1, 32);
+// the partial maps of a run of `form` in io.part: glr_part_rows rows of maxima, then of minima
+void lay_out_maps(const origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form,
+                  GlrSpectralIO *io) {
+  io->nzc = glr_part_rows(ctx, pl, form);
+  io->pmax = io->want_maps ? io->part : nullptr;
+  io->pmin = io->want_maps ? io->part + (size_t)io->nzc * pl->Ny * pl->Nx : nullptr;
 }
 
-// NORMW: the FOLD form of the table kernel between the ends of the cube, the two-product kernel
-// for the 32 channels at either end; the partial maps of the ends follow those of the middle.
-// rg: the spaxels of a band or rectangle (the rows of the partial maps are the whole field's)
-int run_spectral_normw(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectralIO *io,
-                       const NmRange &rg) {
-  int zf0, zf1;
-  mf_fold_range(pl->Nz, &zf0, &zf1);
-  SpectralMfmaArgs a = glr_spectral_mfma_args(pl, io, true);
+// the matrix-core spectral stage of the plan's form over the spaxels of rg (a band or rectangle:
+// the rows of the partial maps are the whole field's)
+int run_spectral_mfma(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form, bool no_fold,
+                      GlrSpectralIO *io, const GlrRange &rg) {
+  lay_out_maps(ctx, pl, form, io);
+  if (form == GLR_SPEC_NORM_MFMA) return origin_spectral_norm_mfma_launch(ctx, pl, *io, rg);
+  const bool normw = form == GLR_SPEC_NORMW;
+  SpectralMfmaArgs a = glr_spectral_mfma_args(pl, io, normw || !no_fold);
+  a.range = rg;
+  if (!normw) return origin_spectral_mfma_launch(ctx, a);
+  // NORMW: the FOLD form of the table kernel between the ends of the cube, the two-product kernel
+  // for the 32 channels at either end; the partial maps of the ends follow those of the middle
   a.rden = a.rdi_s = a.rden_fold = a.sden = nullptr;  // (no class tables: the norm cube instead)
   a.normc = io->norm;
-  a.part_rows = normw_part_rows(ctx, pl);
-  a.s_first = rg.s_first, a.s_count = rg.s_count, a.rx0 = rg.rx0, a.rx1 = rg.rx1;
   if (int rc = origin_spectral_mfma_launch(ctx, a)) return rc;
-  int got = 0;
-  int rc = origin_spectral_norm_mfma_launch_ends(
-      ctx, io->fsf, io->norm, pl->d_atab, pl->d_atab2, pl->d_pwide, pl->K, pl->Nz, pl->Ny, pl->Nx,
-      io->mask, io->correl, io->profile, io->correl_min, io->pmax, io->pmin, zf0, zf1, io->nzc, &got,
-      rg);
-  io->nzc += got;
-  return rc;
-}
-
-// the matrix-core spectral stage of the plan's form over the spaxels of rg
-int run_spectral_mfma(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form, bool no_fold,
-                      GlrSpectralIO *io, const NmRange &rg) {
-  switch (form) {
-    case GLR_SPEC_NORMW:
-      return run_spectral_normw(ctx, pl, io, rg);
-    case GLR_SPEC_NORM_MFMA:
-      return origin_spectral_norm_mfma_launch(ctx, io->fsf, io->norm, pl->d_atab, pl->d_atab2,
-                                              pl->d_pwide, pl->K, pl->Nz, pl->Ny, pl->Nx, io->mask,
-                                              io->correl, io->profile, io->correl_min, io->part,
-                                              io->want_maps, &io->nzc, &io->pmax, &io->pmin, rg);
-    default: {
-      SpectralMfmaArgs a = glr_spectral_mfma_args(pl, io, !no_fold);
-      a.s_first = rg.s_first, a.s_count = rg.s_count, a.rx0 = rg.rx0, a.rx1 = rg.rx1;
-      return origin_spectral_mfma_launch(ctx, a);
-    }
-  }
+  return origin_spectral_norm_mfma_launch_ends(ctx, pl, *io, rg,
+                                               glr_part_rows(ctx, pl, GLR_SPEC_TABLE));
 }
 
 }  // namespace
 
-SpectralMfmaArgs glr_spectral_mfma_args(const origin_glr_plan *pl, GlrSpectralIO *io, bool fold) {
+SpectralMfmaArgs glr_spectral_mfma_args(const origin_glr_plan *pl, const GlrSpectralIO *io,
+                                        bool fold) {
   const bool b16 = pl->precision == 2;
   SpectralMfmaArgs a;
   a.io = io;
@@ -170,7 +152,6 @@ int origin_glr_run_rect(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cub
                    "row band must start at a multiple of 64 and end at one or at Ny");
   ORIGIN_CHECK_ARG(x0 >= 0 && x0 < x1 && x1 <= Nx && x0 % 64 == 0 && (x1 % 64 == 0 || x1 == Nx),
                    "column range must start at a multiple of 64 and end at one or at Nx");
-  const bool whole_rows = x0 == 0 && x1 == Nx;  // (then the waves are those of a run over the field)
   const bool no_fold = glr_no_fold();
   const GlrPaths paths = glr_paths(pl, no_fold);
   if (!paths.prepared) {
@@ -191,15 +172,12 @@ int origin_glr_run_rect(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cub
     if (int rc = origin_fork_begin(ctx, ctx->side, origin_make_side_stream)) return rc;
     std::swap(ctx->stream, ctx->side.stream);
   }
-  int rc = run_spatial(ctx, pl, true, d_cube, work.fsf, y0 / 64, cdiv(y1 - y0, 64), x0 / 64,
-                       cdiv(x1 - x0, 64));
+  const GlrRange rg = {y0, y1, x0, x1};
+  int rc = run_spatial(ctx, pl, true, d_cube, work.fsf, rg);
   if (rc == ORIGIN_OK) {
     ProfScope ps(ctx, K_GLR_SPECTRAL);
     const float *norm = pl->mode == 1 ? pl->d_normc + (size_t)MF_PAD_FRONT * Ny * Nx : nullptr;
     GlrSpectralIO io = {work.fsf, norm, d_mask, d_correl, d_profile, d_correl_min, work.part, true};
-    NmRange rg;
-    rg.s_first = (long)y0 * Nx, rg.s_count = (long)(y1 - y0) * Nx;
-    if (!whole_rows) rg.rx0 = x0, rg.rx1 = x1;
     rc = run_spectral_mfma(ctx, pl, paths.spectral, no_fold, &io, rg);
   }
   if (side) {
@@ -217,19 +195,8 @@ int origin_glr_run_finish(origin_ctx *ctx, origin_glr_plan *pl, float *d_work, f
   if (!d_maxmap && !d_minmap) return ORIGIN_OK;
   const long S = (long)pl->Ny * pl->Nx;
   GlrSpectralIO io = {};
-  // the rows of each partial map: those of the form the bands ran
-  switch (glr_paths(pl, glr_no_fold()).spectral) {
-    case GLR_SPEC_NORMW:
-      io.nzc = normw_part_rows(ctx, pl);
-      break;
-    case GLR_SPEC_NORM_MFMA:
-      io.nzc = origin_spectral_norm_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx);
-      break;
-    default:
-      io.nzc = origin_spectral_mfma_chunks(ctx->num_cu, pl->Nz, pl->Ny, pl->Nx);
-  }
-  io.pmax = GlrWork(pl, d_work).part;
-  io.pmin = io.pmax + (size_t)io.nzc * S;
+  io.part = GlrWork(pl, d_work).part, io.want_maps = true;
+  lay_out_maps(ctx, pl, glr_paths(pl, glr_no_fold()).spectral, &io);  // (the form the bands ran)
   ProfScope ps(ctx, K_SMALL);
   return launch_maxmap_final(ctx, io, S, d_maxmap, d_minmap);
 }
@@ -251,16 +218,16 @@ int origin_glr_run(origin_ctx *ctx, origin_glr_plan *pl, const float *d_cube,
   // (asked now: the eps just measured decides between NORMW and two products)
   const GlrPaths paths = glr_paths(pl, no_fold);
   if (int rc = zero_pads(ctx, pl, d_work, work)) return rc;
-  if (int rc = run_spatial(ctx, pl, paths.spatial_mfma, d_cube, work.fsf)) return rc;
+  const GlrRange whole;
+  if (int rc = run_spatial(ctx, pl, paths.spatial_mfma, d_cube, work.fsf, whole)) return rc;
 
   // ---- spectral stage
   GlrSpectralIO io = {work.fsf, norm, d_mask, d_correl, d_profile, d_correl_min, work.part,
                       d_maxmap || d_minmap};
   {
     ProfScope ps(ctx, K_GLR_SPECTRAL);
-    int rc = paths.spectral_mfma()
-                 ? run_spectral_mfma(ctx, pl, paths.spectral, no_fold, &io, NmRange())
-                 : glr_fp32_spectral(ctx, pl, paths.spectral, &io, &ps);
+    int rc = paths.spectral_mfma() ? run_spectral_mfma(ctx, pl, paths.spectral, no_fold, &io, whole)
+                                   : glr_fp32_spectral(ctx, pl, paths.spectral, &io, &ps);
     if (rc) return rc;
   }
   if (!io.want_maps) return ORIGIN_OK;

@@ -104,8 +104,9 @@ int glr_plan_prepare(origin_ctx *ctx, origin_glr_plan *pl);
 // out (+)= corr2(A * B, taps) per channel; A == NULL: the norm of the weights B
 int glr_fp32_spatial(origin_ctx *ctx, const float *A, const float *B, const float *taps, int Nz,
                      int Ny, int Nx, int P, int accumulate, float *out);
-// what the spectral stage reads and writes, whatever kernel runs it; a launch reports the rows of
-// its partial maps (nzc rows each at pmax / pmin, null without want_maps)
+// what the spectral stage reads and writes, whatever kernel runs it.  The partial maps: nzc rows
+// each at pmax / pmin (null without want_maps) -- the matrix-core forms get them from the driver
+// before their launches (glr_part_rows), the fp32 forms report their own
 struct GlrSpectralIO {
   const float *fsf, *norm;  // padded cubes, channel 0 (norm: plans with a norm cube)
   const uint8_t *mask;
@@ -114,7 +115,7 @@ struct GlrSpectralIO {
   float *correl_min;
   float *part;
   bool want_maps;
-  int nzc = 0;  // set by the launch
+  int nzc = 0;
   float *pmax = nullptr, *pmin = nullptr;
 };
 // forms PACKED (with its border pass, timed as K_GLR_BORDER), FP32 and GENERIC
@@ -124,10 +125,38 @@ int glr_fp32_spectral(origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral fo
 int glr_fp32_border_maps(origin_ctx *ctx, const origin_glr_plan *pl, const float *correl,
                          const float *correl_min, float *maxmap, float *minmap);
 
-// ---- glr_spectral_mfma.hip
+// ---- the matrix-core spectral stage (glr_spectral_mfma.hip, glr_spectral_norm_mfma.hip)
+// The spaxels of a launch: rows y0 .. y1 - 1 and columns x0 .. x1 - 1 of the field, as
+// origin_glr_run_rect takes them; y1 == 0: the whole field.  The spatial stage runs the 64 x 64
+// regions that hold them, the spectral stage what glr_range_resolve makes of them.
+struct GlrRange {
+  int y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+};
+// What a spectral kernel is given: with whole rows the spaxels [s_first, s_end) -- the waves hold
+// the 32 spaxels they hold in a launch over the field, so s_first is a multiple of 32 -- and
+// rx0 = rx1 = 0; with a proper column range a rectangle, columns rx0 .. rx1 - 1 of the rows
+// s_first / Nx .. s_end / Nx - 1, a wave holding 32 consecutive columns of one row.  bx: blocks of
+// `waves` waves along x.
+struct GlrSpaxels {
+  long s_first, s_end, bx;
+  int rx0, rx1;
+};
+int glr_range_resolve(const GlrRange &rg, int Ny, int Nx, int waves, GlrSpaxels *sp);
+// z chunks of a launch over all channels, for blocks of `waves` waves of 32 spaxels: n chunks of
+// len channels.  Those of the WHOLE field of S spaxels, whatever part of it a launch takes: the
+// partial maps of all parts of a run share their layout and a band's z tiles are the whole run's.
+struct GlrChunks {
+  int n, len;
+};
+GlrChunks glr_z_chunks(int num_cu, int Nz, long S, int waves);
+// rows of each partial map of a run of this form: the kernel's z chunks; NORMW: the table
+// kernel's, then the 32-channel end tiles of the two-product kernel
+int glr_part_rows(const origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form);
+
+// glr_spectral_mfma.hip
 struct SpectralMfmaArgs {
   // cube and outputs
-  GlrSpectralIO *io;
+  const GlrSpectralIO *io;
   // tables (fold: nullptr = the exact form everywhere)
   int terms;  // 3: f16 split, 1: bf16
   const uint4 *atab, *atab_fold;
@@ -136,41 +165,22 @@ struct SpectralMfmaArgs {
   int NzP, K, n_narrow, ident;
   // geometry
   int Nz, Ny, Nx, P;
-  // range (s_count > 0: spaxels s_first .. s_first + s_count - 1) or rectangle (rx1 > 0: columns
-  // rx0 .. rx1 - 1 of the range's rows); neither: the whole field
-  long s_first = 0, s_count = 0;
-  int rx0 = 0, rx1 = 0;
-  // NORMW: the norm cube, and the rows of each partial map when other launches add theirs
+  GlrRange range;
+  // NORMW: the norm cube
   const float *normc = nullptr;
-  int part_rows = 0;
 };
 // the tables of the plan's precision; fold: bring the folded tables too
-SpectralMfmaArgs glr_spectral_mfma_args(const origin_glr_plan *pl, GlrSpectralIO *io, bool fold);
+SpectralMfmaArgs glr_spectral_mfma_args(const origin_glr_plan *pl, const GlrSpectralIO *io,
+                                        bool fold);
 int origin_spectral_mfma_launch(origin_ctx *ctx, const SpectralMfmaArgs &a);
 long origin_spectral_mfma_count(int num_cu, int terms, int K, int n_narrow, int Nz, int Ny,
                                 int Nx);
-int origin_spectral_mfma_chunks(int num_cu, int Nz, int Ny, int Nx);
 
-// ---- glr_spectral_norm_mfma.hip: the same stage for plans with an explicit norm cube
-// the spaxels of a launch, as in SpectralMfmaArgs: a range (s_count > 0, s_first a multiple of 32),
-// a rectangle (rx1 > 0: columns rx0 .. rx1 - 1 of the range's rows), or neither: the whole field
-struct NmRange {
-  long s_first = 0, s_count = 0;
-  int rx0 = 0, rx1 = 0;
-};
+// glr_spectral_norm_mfma.hip: the same stage for plans with an explicit norm cube
 int origin_spectral_norm_mfma_max_k();
-// z chunks (rows of each partial map) of a launch over all channels, whatever spaxels it takes
-int origin_spectral_norm_mfma_chunks(int num_cu, int Nz, int Ny, int Nx);
-int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const float *norm,
-                                     const uint4 *atab, const uint4 *atab2, const int *pinfo, int K,
-                                     int Nz, int Ny, int Nx, const uint8_t *mask, float *correl,
-                                     uint8_t *profile, float *correl_min, float *part,
-                                     bool want_maps, int *nzc_out, float **pmax_out,
-                                     float **pmin_out, const NmRange &rg);
-// the end tiles [0, zf0) and [zf1, Nz) of a plan whose other channels run NORMW
-int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const float *fsf, const float *norm,
-                                          const uint4 *atab, const uint4 *atab2, const int *pinfo,
-                                          int K, int Nz, int Ny, int Nx, const uint8_t *mask,
-                                          float *correl, uint8_t *profile, float *correl_min,
-                                          float *pmax, float *pmin, int zf0, int zf1, int prow0,
-                                          int *rows_out, const NmRange &rg);
+int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const origin_glr_plan *pl,
+                                     const GlrSpectralIO &io, const GlrRange &rg);
+// the end tiles [0, zf0) and [zf1, Nz) of a plan whose other channels run NORMW (mf_fold_range);
+// their partial maps from row prow0 on
+int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const origin_glr_plan *pl,
+                                          const GlrSpectralIO &io, const GlrRange &rg, int prow0);

@@ -1,7 +1,9 @@
 // GLR matched filter: the plan (glr.hip has the algebra and the runs).  A plan holds what depends on
 // the PSFs, the weight maps and the profiles alone: the taps in the layouts of every kernel, the
 // border-class normalisation tables of an unweighted field, the FOLD tables and their eps test,
-// and the norm cube of a weighted one.
+// and the norm cube of a weighted one.  It also says what a plan runs (glr_paths_at) and holds the
+// launch geometry the two matrix-core spectral kernels share: the spaxels of a range, the z chunks
+// and the rows of the partial maps.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -473,6 +475,56 @@ int build_fold_tables(origin_glr_plan *pl, const std::vector<double> &fold_a) {
 
 }  // namespace
 
+// ---- the launch geometry the two matrix-core spectral kernels share
+int glr_range_resolve(const GlrRange &rg, int Ny, int Nx, int waves, GlrSpaxels *sp) {
+  const GlrRange r = rg.y1 > 0 ? rg : GlrRange{0, Ny, 0, Nx};
+  const bool rect = r.x0 > 0 || r.x1 < Nx;
+  const long s_first = (long)r.y0 * Nx, s_end = (long)r.y1 * Nx;
+  if (r.y0 < 0 || r.y0 >= r.y1 || r.y1 > Ny || (!rect && s_first % 32 != 0)) {
+    origin_set_error("spectral MFMA stage: bad spaxel range");
+    return ORIGIN_E_ARG;
+  }
+  if (r.x0 < 0 || r.x0 >= r.x1 || r.x1 > Nx) {
+    origin_set_error("spectral MFMA stage: bad rectangle");
+    return ORIGIN_E_ARG;
+  }
+  // columns (32 spaxels x one z chunk): one per wave
+  const long ncols = rect ? (long)(r.y1 - r.y0) * cdiv(r.x1 - r.x0, 32) : cdiv(s_end - s_first, 32);
+  *sp = {s_first, s_end, cdiv(ncols, waves), rect ? r.x0 : 0, rect ? r.x1 : 0};
+  return ORIGIN_OK;
+}
+
+// One block per CU at a time (LDS): the number of z chunks is picked so that the blocks fill whole
+// rounds of the chip -- useful channel slots / (rounds x CUs x (chunk length + ~one tile of
+// start-up per block)); chunks are whole 32-channel tiles, at most 64 of them (partial maps).
+GlrChunks glr_z_chunks(int num_cu, int Nz, long S, int waves) {
+  const long bx = cdiv(S, 32 * waves);
+  const int ncu = std::max(1, num_cu);
+  int nzm = 1;
+  double best_eff = 0.0;
+  for (int n = 1; n <= std::min(64, std::max(1, cdiv(Nz, 64))); ++n) {
+    const int zc = (cdiv(Nz, n) + 31) / 32 * 32;
+    const long blocks = bx * cdiv(Nz, zc);
+    const long rounds = (blocks + ncu - 1) / ncu;
+    const double eff = (double)bx * Nz / ((double)rounds * ncu * (zc + 32));
+    if (eff > best_eff * 1.0001) best_eff = eff, nzm = n;
+  }
+  const int zcm = (cdiv(Nz, nzm) + 31) / 32 * 32;
+  return {cdiv(Nz, zcm), zcm};
+}
+
+int glr_part_rows(const origin_ctx *ctx, const origin_glr_plan *pl, GlrSpectral form) {
+  const long S = (long)pl->Ny * pl->Nx;
+  if (form == GLR_SPEC_NORM_MFMA) return glr_z_chunks(ctx->num_cu, pl->Nz, S, NM_WAVES).n;
+  int rows = glr_z_chunks(ctx->num_cu, pl->Nz, S, MF_WAVES).n;
+  if (form == GLR_SPEC_NORMW) {
+    int zf0, zf1;
+    mf_fold_range(pl->Nz, &zf0, &zf1);
+    rows += cdiv(zf0, 32) + cdiv(pl->Nz - zf1, 32);
+  }
+  return rows;
+}
+
 GlrPaths glr_paths_at(const origin_glr_plan *pl, int precision, bool no_fold) {
   GlrPaths p;
   p.prepared = pl->mode == 0 || (pl->normc_ready && pl->normw_checked);
@@ -488,11 +540,10 @@ GlrPaths glr_paths_at(const origin_glr_plan *pl, int precision, bool no_fold) {
   // at either end of the cube; the partial maps of both must fit their 64 rows
   int zf0, zf1;
   mf_fold_range(pl->Nz, &zf0, &zf1);
-  const int end_rows = cdiv(zf0, 32) + cdiv(pl->Nz - zf1, 32);
   const bool normw =
       norm_tables && pl->normw_checked && pl->fold_eps <= MF_FOLD_EPS && pl->d_atab_fold &&
       zf1 > zf0 && !no_fold && pl->K > 2 &&  // (the FOLD pair loop peels two pairs)
-      origin_spectral_mfma_chunks(pl->ctx->num_cu, pl->Nz, pl->Ny, pl->Nx) + end_rows <= 64;
+      glr_part_rows(pl->ctx, pl, GLR_SPEC_NORMW) <= 64;
   if (normw) p.spectral = GLR_SPEC_NORMW;
   else if (norm_tables && precision == 1) p.spectral = GLR_SPEC_NORM_MFMA;
   else if (mc && pl->mode == 0 && pl->d_rdi) p.spectral = GLR_SPEC_TABLE;

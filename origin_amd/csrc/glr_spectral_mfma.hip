@@ -849,49 +849,16 @@ __global__ __launch_bounds__(64 * MF_WAVES, 1) void spectral_mfma2_kernel(
 
 }  // namespace
 
-// Grid of the spectral kernel: bx blocks of MF_WAVES waves (32 spaxels each) x nzm chunks of zcm
-// channels.  One block per CU at a time (LDS): the number of z chunks is picked so that the
-// blocks fill whole rounds of the chip -- useful channel slots / (rounds x CUs x (chunk length +
-// ~one tile of start-up per block)); chunks are whole 32-channel tiles, at most 64 of them
-// (partial maps).  Shared by the launch and by origin_spectral_mfma_count.
-static void sm_geometry(int num_cu, int Nz, long S, long *bx_out, int *nzm_out, int *zcm_out) {
-  const long bx = cdiv(S, 32 * MF_WAVES);
-  const int ncu = std::max(1, num_cu);
-  int nzm = 1;
-  double best_eff = 0.0;
-  for (int n = 1; n <= std::min(64, std::max(1, cdiv(Nz, 64))); ++n) {
-    const int zc = (cdiv(Nz, n) + 31) / 32 * 32;
-    const long blocks = bx * cdiv(Nz, zc);
-    const long rounds = (blocks + ncu - 1) / ncu;
-    const double eff = (double)bx * Nz / ((double)rounds * ncu * (zc + 32));
-    if (eff > best_eff * 1.0001) best_eff = eff, nzm = n;
-  }
-  const int zcm = (cdiv(Nz, nzm) + 31) / 32 * 32;
-  *bx_out = bx;
-  *nzm_out = cdiv(Nz, zcm);
-  *zcm_out = zcm;
-}
-
 // MFMA instructions one launch issues (what SQ_INSTS_MFMA counts): every wave that holds a
 // spaxel walks all 32-channel tiles of its chunk; a tile is two 16-channel halves, a half runs
 // every profile pair (slots 2p, 2p+1 of the processing order, narrow profiles first) with 3
 // k-steps (both narrow: window blocks 1..3) or 5, `terms` MFMAs per k-step.
-// z chunks (rows of the partial maps) of a launch
-int origin_spectral_mfma_chunks(int num_cu, int Nz, int Ny, int Nx) {
-  long bx;
-  int nzm, zcm;
-  sm_geometry(num_cu, Nz, (long)Ny * Nx, &bx, &nzm, &zcm);
-  return nzm;
-}
-
 long origin_spectral_mfma_count(int num_cu, int terms, int K, int n_narrow, int Nz, int Ny,
                                 int Nx) {
   const long S = (long)Ny * Nx;
-  long bx;
-  int nzm, zcm;
-  sm_geometry(num_cu, Nz, S, &bx, &nzm, &zcm);
+  const GlrChunks zc = glr_z_chunks(num_cu, Nz, S, MF_WAVES);
   long tiles = 0;  // 32-channel tiles per wave, over all chunks
-  for (int c = 0; c < nzm; ++c) tiles += cdiv(std::min(zcm, Nz - c * zcm), 32);
+  for (int c = 0; c < zc.n; ++c) tiles += cdiv(std::min(zc.len, Nz - c * zc.len), 32);
   long ksteps = 0;
   for (int p = 0; p < (K + 1) / 2; ++p) {
     const int sb = std::min(2 * p + 1, K - 1);
@@ -901,37 +868,16 @@ long origin_spectral_mfma_count(int num_cu, int terms, int K, int n_narrow, int 
   return waves * tiles * 2 * ksteps * terms;
 }
 
-// Launch: a wave = 32 spaxels x 32-channel tiles (two 16-channel halves); z chunks sized to give every CU several blocks
-// (one block per CU at a time: K * (4.5 KiB + MF_WAVES * 128 B) of LDS).  Reports the number of z
-// chunks (rows of pmax / pmin) in a.io.
+// Launch: the grid is the range's blocks of MF_WAVES waves (32 spaxels each) x the z chunks of the
+// whole field (glr_z_chunks); a wave marches its chunk in 32-channel tiles (two 16-channel
+// halves).  One block per CU at a time: K * (4.5 KiB + MF_WAVES * 128 B) of LDS.  The partial maps
+// go to the rows 0 .. of a.io's pmax / pmin.
 int origin_spectral_mfma_launch(origin_ctx *ctx, const SpectralMfmaArgs &a) {
-  GlrSpectralIO *io = a.io;
+  const GlrSpectralIO *io = a.io;
   const int K = a.K, Nz = a.Nz, Nx = a.Nx;
-  const long S = (long)a.Ny * Nx;
-  long bx;
-  int nzm, zcm;
-  // (the z chunks are those of a launch over the whole field, whatever part of it this one takes:
-  // the partial maps of all parts of a run share their layout)
-  sm_geometry(ctx->num_cu, Nz, S, &bx, &nzm, &zcm);
-  long s_first = a.s_first, s_count = a.s_count;
-  if (s_count <= 0) s_first = 0, s_count = S;
-  if ((a.rx1 <= 0 && s_first % 32 != 0) || s_first < 0 || s_first + s_count > S) {
-    origin_set_error("spectral MFMA kernel: bad spaxel range");
-    return ORIGIN_E_ARG;
-  }
-  long ncols = cdiv(s_count, 32);  // columns (32 spaxels x one z chunk): one per wave
-  long s_end = s_first + s_count;
-  if (a.rx1 > 0) {  // rectangle: whole rows s_first / Nx .. , columns rx0 .. rx1 - 1
-    if (s_first % Nx != 0 || s_count % Nx != 0 || a.rx0 < 0 || a.rx0 >= a.rx1 || a.rx1 > Nx) {
-      origin_set_error("spectral MFMA kernel: bad rectangle");
-      return ORIGIN_E_ARG;
-    }
-    ncols = (s_count / Nx) * (long)cdiv(a.rx1 - a.rx0, 32);
-  }
-  bx = cdiv(ncols, MF_WAVES);
-  // (part_rows: rows of each partial map when other launches add theirs behind this one's)
-  float *pmax = io->want_maps ? io->part : nullptr;
-  float *pmin = io->want_maps ? io->part + (size_t)std::max(nzm, a.part_rows) * S : nullptr;
+  const GlrChunks zc = glr_z_chunks(ctx->num_cu, Nz, (long)a.Ny * Nx, MF_WAVES);
+  GlrSpaxels sp;
+  if (int rc = glr_range_resolve(a.range, a.Ny, Nx, MF_WAVES, &sp)) return rc;
   const int Kp = K + (K & 1);
   // (+ one profile of slack: the last stage requests the fragments of a pair that is not there)
   const size_t lds = std::max((size_t)Kp * MF_PROF_BYTES + (size_t)K * MF_WAVES * MF_RD_BYTES,
@@ -976,17 +922,15 @@ int origin_spectral_mfma_launch(origin_ctx *ctx, const SpectralMfmaArgs &a) {
   const uint8_t *mask = io->mask;
   float *correl = io->correl, *correl_min = io->correl_min;
   uint8_t *profile = io->profile;
-  int NzP = a.NzP, k_K = K, k_NP = NP, k_Nz = Nz, Ny = a.Ny, k_Nx = Nx, P = a.P, k_zcm = zcm;
-  int nN = a.n_narrow, rx0 = a.rx0, rx1 = a.rx1;
+  float *pmax = io->pmax, *pmin = io->pmin;
+  int NzP = a.NzP, k_K = K, k_NP = NP, k_Nz = Nz, Ny = a.Ny, k_Nx = Nx, P = a.P, k_zcm = zc.len;
+  int nN = a.n_narrow;
   void *args[] = {&fsf, &k_rden, &rdi_s, &NzP, &k_atab, &pinfo, &k_K, &k_NP, &k_Nz, &Ny, &k_Nx, &P,
                   &k_zcm, &mask, &correl, &profile, &correl_min, &pmax, &pmin, &k_sden, &zf0, &zf1,
-                  &nN, &s_first, &s_end, &rx0, &rx1};
-  ORIGIN_HIP(hipLaunchKernel(fn, dim3((unsigned)bx, (unsigned)nzm), dim3(64 * MF_WAVES), args,
+                  &nN, &sp.s_first, &sp.s_end, &sp.rx0, &sp.rx1};
+  ORIGIN_HIP(hipLaunchKernel(fn, dim3((unsigned)sp.bx, (unsigned)zc.n), dim3(64 * MF_WAVES), args,
                              fold ? std::max(lds, lds_fold) : lds, ctx->stream));
   ORIGIN_LAUNCH_CHECK();
-  io->nzc = nzm;
-  io->pmax = pmax;
-  io->pmin = pmin;
   return ORIGIN_OK;
 }
 

@@ -27,10 +27,11 @@
 // kernel keeps the 32 channels at either end (origin_spectral_norm_mfma_launch_ends) and the plans
 // whose eps is too large.
 //
-// Like the table kernel a launch takes the whole field, a range of spaxels (a row band: the waves
-// hold the spaxels they hold in a launch over the field, so a run in bands is bit for bit the run)
-// or a rectangle of 64 x 64 regions (a wave holds 32 columns of one row); the z chunks and the
-// rows of the partial maps are those of the whole field whatever part a launch takes.
+// Like the table kernel a launch takes a GlrRange (glr_plan.h): the whole field, a range of spaxels
+// (a row band: the waves hold the spaxels they hold in a launch over the field, so a run in bands
+// is bit for bit the run) or a rectangle of 64 x 64 regions (a wave holds 32 columns of one row);
+// the z chunks (glr_z_chunks at NM_WAVES waves per block) and the rows of the partial maps are
+// those of the whole field whatever part a launch takes.
 //
 // This is the straightforward form: no software pipelining of the epilogue under the next pair's
 // MFMAs, the whole 96-channel window of both cubes converted per tile, two waves per SIMD.  It
@@ -41,7 +42,7 @@
 
 namespace {
 
-constexpr int NW = 8;         // waves per block
+constexpr int NW = NM_WAVES;  // waves per block
 constexpr int NM_MAX_K = 13;  // profiles per launch: 13 * 2 * 4608 B = 117 KiB of LDS
 
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
@@ -321,44 +322,26 @@ __global__ __launch_bounds__(64 * NW, 1) void spectral_norm_mfma_kernel(
   }
 }
 
+// the channels of a launch: [z0, z1) in chunks of `chunk` (grid.y), partial maps from row row0 on
+struct NmSpan {
+  int z0, z1, chunk, row0;
+};
+
 }  // namespace
 
-// the spaxels of a launch, as glr_spectral_mfma.hip takes them: s_count > 0: the range [s_first,
-// s_first + s_count), s_first a multiple of 32; rx1 > 0: columns rx0 .. rx1 - 1 of the range's
-// rows; neither: the whole field.  Fills the kernel's (s_first, s_end) and the blocks along x.
-static int nm_range(const NmRange &rg, int Ny, int Nx, long *s_first, long *s_end, long *bx) {
-  const long S = (long)Ny * Nx;
-  long s0 = rg.s_first, n = rg.s_count;
-  if (n <= 0) s0 = 0, n = S;
-  if ((rg.rx1 <= 0 && s0 % 32 != 0) || s0 < 0 || s0 + n > S) {
-    origin_set_error("spectral norm MFMA kernel: bad spaxel range");
-    return ORIGIN_E_ARG;
-  }
-  long ncols = cdiv(n, 32);  // columns (32 spaxels x one z chunk): one per wave
-  if (rg.rx1 > 0) {
-    if (s0 % Nx != 0 || n % Nx != 0 || rg.rx0 < 0 || rg.rx0 >= rg.rx1 || rg.rx1 > Nx) {
-      origin_set_error("spectral norm MFMA kernel: bad rectangle");
-      return ORIGIN_E_ARG;
-    }
-    ncols = (n / Nx) * (long)cdiv(rg.rx1 - rg.rx0, 32);
-  }
-  *s_first = s0, *s_end = s0 + n, *bx = cdiv(ncols, NW);
-  return ORIGIN_OK;
-}
-
-// the launches over the halves of the profile list for the channels [zstart, zstop) in chunks of
-// zcm (grid.y = nchunks) and the spaxels of rg; partial maps from row prow0 on
-static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const uint4 *atab,
-                     const uint4 *atab2, const int *pinfo, int K, int Nz, int Ny, int Nx,
-                     const uint8_t *mask, float *correl, uint8_t *profile, float *correl_min,
-                     float *pmax, float *pmin, const NmRange &rg, int nchunks, int zcm, int zstart,
-                     int zstop, int prow0) {
+// the launches over the halves of the profile list for the channels of zs and the spaxels of rg.
+// io.fsf and io.norm: cubes padded with MF_PAD_FRONT zero channels in front and MF_PAD_BACK behind
+// (the pointers are to channel 0); the plan's f16 tap and tap^2 tables are in processing order
+// (glr_plan.hip), d_pwide the profile of each slot.
+static int nm_passes(origin_ctx *ctx, const origin_glr_plan *pl, const GlrSpectralIO &io,
+                     const GlrRange &rg, const NmSpan &zs) {
+  const int K = pl->K;
   if (K > 2 * NM_MAX_K) {
     origin_set_error("spectral norm MFMA kernel: %d profiles (at most %d)", K, 2 * NM_MAX_K);
     return ORIGIN_E_ARG;
   }
-  long s_first, s_end, bx;
-  if (int rc = nm_range(rg, Ny, Nx, &s_first, &s_end, &bx)) return rc;
+  GlrSpaxels sp;
+  if (int rc = glr_range_resolve(rg, pl->Ny, pl->Nx, NM_WAVES, &sp)) return rc;
   const int npass = K > NM_MAX_K ? 2 : 1;
   const int K0 = npass == 2 ? (K / 2 + 1) / 2 * 2 : K;  // an even count first: whole pairs
   static OriginPerDeviceOnce attr_once;
@@ -370,23 +353,21 @@ static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const
                          ORIGIN_HIP(hipFuncSetAttribute(
                              (const void *)spectral_norm_mfma_kernel<true>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, dyn)));
+  const dim3 grid((unsigned)sp.bx, cdiv(zs.z1 - zs.z0, zs.chunk)), block(64 * NM_WAVES);
   for (int pass = 0; pass < npass; ++pass) {  // (both passes over the same spaxels)
     const int s0 = pass == 0 ? 0 : K0, Kl = pass == 0 ? K0 : K - K0;
     const bool last = pass == npass - 1;
     const size_t lds = (size_t)Kl * 2 * MF_PROF_BYTES;
-    const uint4 *ta = atab + (size_t)s0 * (MF_PROF_BYTES / 16);
-    const uint4 *tb = atab2 + (size_t)s0 * (MF_PROF_BYTES / 16);
-    const uint8_t *mk = last ? mask : nullptr;
-    float *qmax = last ? pmax : nullptr, *qmin = last ? pmin : nullptr;
-    dim3 grid((unsigned)bx, nchunks), block(64 * NW);
-    if (pass == 0)
-      hipLaunchKernelGGL(spectral_norm_mfma_kernel<false>, grid, block, lds, ctx->stream, fsf, norm,
-                         ta, tb, pinfo + s0, Kl, Nz, Ny, Nx, zcm, mk, correl, profile, correl_min,
-                         qmax, qmin, zstart, zstop, prow0, s_first, s_end, rg.rx0, rg.rx1);
-    else
-      hipLaunchKernelGGL(spectral_norm_mfma_kernel<true>, grid, block, lds, ctx->stream, fsf, norm,
-                         ta, tb, pinfo + s0, Kl, Nz, Ny, Nx, zcm, mk, correl, profile, correl_min,
-                         qmax, qmin, zstart, zstop, prow0, s_first, s_end, rg.rx0, rg.rx1);
+    const uint4 *ta = pl->d_atab + (size_t)s0 * (MF_PROF_BYTES / 16);
+    const uint4 *tb = pl->d_atab2 + (size_t)s0 * (MF_PROF_BYTES / 16);
+    // (the second pass merges with what the first left; mask and maps belong to the last)
+    const auto kernel =
+        pass == 0 ? spectral_norm_mfma_kernel<false> : spectral_norm_mfma_kernel<true>;
+    hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, io.fsf, io.norm, ta, tb,
+                       pl->d_pwide + s0, Kl, pl->Nz, pl->Ny, pl->Nx, zs.chunk,
+                       last ? io.mask : nullptr, io.correl, io.profile, io.correl_min,
+                       last ? io.pmax : nullptr, last ? io.pmin : nullptr, zs.z0, zs.z1, zs.row0,
+                       sp.s_first, sp.s_end, sp.rx0, sp.rx1);
     ORIGIN_LAUNCH_CHECK();
   }
   return ORIGIN_OK;
@@ -394,79 +375,22 @@ static int nm_passes(origin_ctx *ctx, const float *fsf, const float *norm, const
 
 int origin_spectral_norm_mfma_max_k() { return 2 * NM_MAX_K; }
 
-// z chunks of a launch over all channels: whole rounds of the chip for the blocks of the WHOLE
-// field, whatever part of it a launch takes -- the partial maps of all parts of a run share their
-// layout and a band's z tiles are the whole run's
-static void nm_geometry(int num_cu, int Nz, long S, int *nzm_out, int *zcm_out) {
-  const long bx = cdiv(S, 32 * NW);
-  const int ncu = std::max(1, num_cu);
-  int nzm = 1;
-  double best_eff = 0.0;
-  for (int n = 1; n <= std::min(64, std::max(1, cdiv(Nz, 64))); ++n) {
-    const int zc = (cdiv(Nz, n) + 31) / 32 * 32;
-    const long blocks = bx * cdiv(Nz, zc);
-    const long rounds = (blocks + ncu - 1) / ncu;
-    const double eff = (double)bx * Nz / ((double)rounds * ncu * (zc + 32));
-    if (eff > best_eff * 1.0001) best_eff = eff, nzm = n;
-  }
-  const int zcm = (cdiv(Nz, nzm) + 31) / 32 * 32;
-  *nzm_out = cdiv(Nz, zcm);
-  *zcm_out = zcm;
-}
-
-int origin_spectral_norm_mfma_chunks(int num_cu, int Nz, int Ny, int Nx) {
-  int nzm, zcm;
-  nm_geometry(num_cu, Nz, (long)Ny * Nx, &nzm, &zcm);
-  return nzm;
-}
-
-// fsf and norm: cubes padded with MF_PAD_FRONT zero channels in front and MF_PAD_BACK behind (the
-// pointers are to channel 0).  atab / atab2: tap and tap^2 tables in processing order (glr.hip),
-// pinfo the profile of each slot.  Two launches over the halves of the profile list.
-int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const float *fsf, const float *norm,
-                                     const uint4 *atab, const uint4 *atab2, const int *pinfo, int K,
-                                     int Nz, int Ny, int Nx, const uint8_t *mask, float *correl,
-                                     uint8_t *profile, float *correl_min, float *part,
-                                     bool want_maps, int *nzc_out, float **pmax_out,
-                                     float **pmin_out, const NmRange &rg) {
-  const long S = (long)Ny * Nx;
-  int nzm, zcm;
-  nm_geometry(ctx->num_cu, Nz, S, &nzm, &zcm);
-  float *pmax = want_maps ? part : nullptr;
-  float *pmin = want_maps ? part + (size_t)nzm * S : nullptr;
-  int rc = nm_passes(ctx, fsf, norm, atab, atab2, pinfo, K, Nz, Ny, Nx, mask, correl, profile,
-                     correl_min, pmax, pmin, rg, nzm, zcm, 0, Nz, 0);
-  if (rc) return rc;
-  *nzc_out = nzm;
-  *pmax_out = pmax;
-  *pmin_out = pmin;
-  return ORIGIN_OK;
+// all channels, in the z chunks of the whole field
+int origin_spectral_norm_mfma_launch(origin_ctx *ctx, const origin_glr_plan *pl,
+                                     const GlrSpectralIO &io, const GlrRange &rg) {
+  const GlrChunks zc = glr_z_chunks(ctx->num_cu, pl->Nz, (long)pl->Ny * pl->Nx, NM_WAVES);
+  return nm_passes(ctx, pl, io, rg, {0, pl->Nz, zc.len, 0});
 }
 
 // The 32-channel tiles at either end of the cube only -- [0, zf0) and [zf1, Nz) -- for plans whose
 // other channels run the FOLD form of the table kernel (glr_spectral_mfma.hip, NORMW).  Partial
-// maps go to rows prow0 (front) and prow0 + 1 .. (back, chunks of 32).
-int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const float *fsf, const float *norm,
-                                          const uint4 *atab, const uint4 *atab2, const int *pinfo,
-                                          int K, int Nz, int Ny, int Nx, const uint8_t *mask,
-                                          float *correl, uint8_t *profile, float *correl_min,
-                                          float *pmax, float *pmin, int zf0, int zf1, int prow0,
-                                          int *rows_out, const NmRange &rg) {
-  int rows = 0;
-  if (zf0 > 0) {
-    const int n = cdiv(zf0, 32);
-    int rc = nm_passes(ctx, fsf, norm, atab, atab2, pinfo, K, Nz, Ny, Nx, mask, correl, profile,
-                       correl_min, pmax, pmin, rg, n, 32, 0, zf0, prow0);
-    if (rc) return rc;
-    rows += n;
-  }
-  if (zf1 < Nz) {
-    const int n = cdiv(Nz - zf1, 32);
-    int rc = nm_passes(ctx, fsf, norm, atab, atab2, pinfo, K, Nz, Ny, Nx, mask, correl, profile,
-                       correl_min, pmax, pmin, rg, n, 32, zf1, Nz, prow0 + rows);
-    if (rc) return rc;
-    rows += n;
-  }
-  *rows_out = rows;
+// maps go to rows prow0 .. (front), then the back's (chunks of 32).
+int origin_spectral_norm_mfma_launch_ends(origin_ctx *ctx, const origin_glr_plan *pl,
+                                          const GlrSpectralIO &io, const GlrRange &rg, int prow0) {
+  int zf0, zf1;
+  mf_fold_range(pl->Nz, &zf0, &zf1);
+  if (zf0 > 0)
+    if (int rc = nm_passes(ctx, pl, io, rg, {0, zf0, 32, prow0})) return rc;
+  if (zf1 < pl->Nz) return nm_passes(ctx, pl, io, rg, {zf1, pl->Nz, 32, prow0 + cdiv(zf0, 32)});
   return ORIGIN_OK;
 }
