@@ -25,9 +25,12 @@
 // per iteration the host reads back two ints per area to size the launches.
 //
 // u comes from the Gram matrix G = Xp^T Xp (float64 MFMA, the only matrix-shaped
-// contraction of the path): its leading eigenvector v (device Lanczos with full
-// re-orthogonalisation, restarted until the Ritz residual is at rounding level) gives
-// u = Xp v / |Xp v|.  SURVEY.md section 7 (hard part 1): the loop is threshold driven, so the
+// contraction of the path): its leading eigenvector v, converged until the residual is at
+// rounding level, gives u = Xp v / |Xp v|.  pca_eig.hip picks the solver by the size of the
+// iteration's largest matrix: up to 96 columns repeated squaring on the matrix cores
+// (eig_power_kernel), up to 512 plain Lanczos with the matrix resident on the CU
+// (lanczos_plain_kernel), above that restarted Lanczos with full re-orthogonalisation
+// (lanczos_kernel).  SURVEY.md section 7 (hard part 1): the loop is threshold driven, so the
 // eigen-solve must be converged; everything that feeds it is float64, only the cube is f32.
 //
 // A block never straddles two areas, so per-area vectors (b, u) are wave-uniform.
@@ -87,53 +90,119 @@ struct BlockScan {
   }
 };
 
-__device__ __forceinline__ void pca_select_body(
-    const int *__restrict__ spx, const long *__restrict__ spx_off, const double *__restrict__ test,
-    const double *__restrict__ thr_, double noise_pop, int itermax, int *__restrict__ active,
-    int *__restrict__ nbiter, int *__restrict__ nstop, int *__restrict__ mapO2,
-    int *__restrict__ nuis, int *__restrict__ bg, int *__restrict__ nuis_pos,
-    int *__restrict__ bg_pos, int *__restrict__ n_out, int *__restrict__ nb_out, int lds_cap) {
+// What a selection launch works on: the area lists, the O2 values and thresholds, the per-area
+// state, the lists it writes and where the counts go.  One block per area.
+struct SelectArgs {
+  const int *spx;       // spaxel lists of the areas, area a at [spx_off[a], spx_off[a + 1])
+  const long *spx_off;
+  const double *test, *thr;
+  double noise_pop;
+  int itermax;
+  int *active, *nbiter, *nstop, *mapO2;
+  int *nuis, *bg, *nuis_pos, *bg_pos;  // nuisance / background spaxels and their list positions
+  int *n_out, *nb_out;
+  // changes of the background set against the previous iteration (bmean_kernel), kept by the
+  // register-resident kernel only: membership flags, signed list of changes, their number per area
+  uint8_t *inB;
+  int *dlist, *ndiff;
+  // select_publish: mapped host memory for the counts, the device counter of finished blocks and
+  // the generation of this launch
+  int *host_out;
+  unsigned *counter;
+  int gen;
+};
+
+// ---- the rules both selection kernels share (side effects by thread 0, in the reference's order)
+// the area stops iterating
+__device__ __forceinline__ void select_stop(const SelectArgs &s, int a) {
+  if (threadIdx.x == 0) s.active[a] = 0, s.n_out[a] = 0, s.nb_out[a] = 0;
+}
+
+// entry: an area that has stopped reports zero counts; returns whether the area still iterates
+__device__ __forceinline__ bool select_enter(const SelectArgs &s, int a) {
+  if (s.active[a]) return true;
+  if (threadIdx.x == 0) s.n_out[a] = 0, s.nb_out[a] = 0;
+  return false;
+}
+
+// nbiter += 1; if nbiter > itermax: nstop += 1; break                            (lib :900-905)
+// (mapO2[pypx] += 1 comes before it, lib :901.)  s_it: an int in LDS; returns whether the area stops.
+__device__ __forceinline__ bool select_itermax_stop(const SelectArgs &s, int a, int *s_it) {
+  if (threadIdx.x == 0) {
+    const int it = s.nbiter[a] + 1;
+    s.nbiter[a] = it;
+    *s_it = it;
+  }
+  __syncthreads();
+  if (*s_it <= s.itermax) return false;
+  if (threadIdx.x == 0) atomicAdd(s.nstop, 1);
+  select_stop(s, a);
+  return true;
+}
+
+// nb = 1 + int(len(nind) / Noise_population), clipped by the slice [:nb]         (lib :914-917)
+__device__ __forceinline__ int select_nb(int ncand, double noise_pop) {
+  const int nb = 1 + (int)floor((double)ncand / noise_pop);
+  return nb > ncand ? ncand : nb;
+}
+
+// One radix pass's pick, by wave 0: the bucket of hist[256] that holds rank *s_remaining, through a
+// 64-lane prefix scan of four buckets per lane.  Leaves the rank inside that bucket in
+// *s_remaining and `prefix` with the bucket's digit at `shift` in *s_prefix; s_done (may be null):
+// whether the bucket holds a single element, which is then the answer.
+__device__ __forceinline__ void select_pick_bucket(const int *hist, unsigned long long prefix,
+                                                   int shift, int *s_remaining,
+                                                   unsigned long long *s_prefix, int *s_done) {
+  const int lane = threadIdx.x;
+  const int rem0 = *s_remaining;
+  const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2],
+            h3 = hist[4 * lane + 3];
+  const int mine = h0 + h1 + h2 + h3;
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += v;
+  }
+  const int excl = incl - mine;
+  if (rem0 >= excl && rem0 < incl) {  // exactly one lane
+    int rem = rem0 - excl, b = 4 * lane, hb = h0;
+    if (rem >= h0) {
+      rem -= h0, ++b, hb = h1;
+      if (rem >= h1) {
+        rem -= h1, ++b, hb = h2;
+        if (rem >= h2) rem -= h2, ++b, hb = h3;
+      }
+    }
+    *s_remaining = rem;
+    *s_prefix = prefix | ((unsigned long long)b << shift);
+    if (s_done) *s_done = hb == 1;  // (then rem == 0)
+  }
+}
+
+// the counts of an area that goes on; if x_red.shape[1] == 1: break              (lib :927-928)
+__device__ __forceinline__ void select_finish(const SelectArgs &s, int a, int n, int nb) {
+  if (threadIdx.x != 0) return;
+  s.nb_out[a] = nb;
+  if (n == 1) s.active[a] = 0;
+  s.n_out[a] = n == 1 ? 0 : n;
+}
+
+// The general kernel, for areas of any size: the O2 values are streamed from memory in every pass,
+// one block scan per 1024-entry chunk.
+__device__ __forceinline__ void pca_select_body(const SelectArgs &s) {
   __shared__ int wtot[16];
   __shared__ int hist[256];
   __shared__ unsigned long long s_prefix;
-  __shared__ int s_remaining, s_ncand;
-  extern __shared__ double tcache[];  // the area's O2 values (when they fit: lds_cap > 0)
+  __shared__ int s_remaining, s_it;
   const int a = blockIdx.x;
   const int tid = threadIdx.x;
-  const long o0 = spx_off[a];
-  const int ns = (int)(spx_off[a + 1] - o0);
-  if (!active[a]) {
-    if (tid == 0) n_out[a] = 0, nb_out[a] = 0;
-    return;
-  }
-  const double thr = thr_[a];
+  const long o0 = s.spx_off[a];
+  const int ns = (int)(s.spx_off[a + 1] - o0);
+  if (!select_enter(s, a)) return;
+  const double thr = s.thr[a];
   BlockScan scan{wtot};
-  // the selection makes ~11 passes over the area's O2 values: keep them (and the spaxel list)
-  // in LDS.  Filling is two batches of independent loads (index, then value): every dependent
-  // global read costs an L2 round trip of ~0.7 us.
-  const bool cached = ns <= lds_cap;
-  int *scache = reinterpret_cast<int *>(tcache + lds_cap);
-  if (cached) {
-    for (int c0 = 0; c0 < ns; c0 += 8 * 1024) {
-      int sp[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int i = c0 + tid + 1024 * e;
-        sp[e] = i < ns ? spx[o0 + i] : -1;
-      }
-      double tv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) tv[e] = sp[e] >= 0 ? test[sp[e]] : 0.0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int i = c0 + tid + 1024 * e;
-        if (i < ns) tcache[i] = tv[e], scache[i] = sp[e];
-      }
-    }
-    __syncthreads();
-  }
-  auto tval = [&](int i) -> double { return cached ? tcache[i] : test[spx[o0 + i]]; };
-  auto sval = [&](long i) -> int { return cached ? scache[i] : spx[o0 + i]; };
+  auto tval = [&](int i) -> double { return s.test[s.spx[o0 + i]]; };
 
   // ---- pass 1: nuisance compaction in index order (np.where(test > thr)), candidates count
   int n = 0, ncand = 0;
@@ -142,14 +211,14 @@ __device__ __forceinline__ void pca_select_body(
     const bool valid = i < ns;
     const double t = valid ? tval(i) : 0.0;
     const bool isn = valid && (t > thr);
-    const int sp = isn ? sval(i) : 0;
+    const int sp = isn ? s.spx[o0 + i] : 0;
     const bool cand = valid && (t > 0.0) && (t <= thr);
     int tot;
     const int r = scan.exclusive(isn, tot);
     if (isn) {
-      nuis[o0 + n + r] = sp;
-      nuis_pos[o0 + n + r] = (int)(o0 + i);
-      mapO2[sp] += 1;  // mapO2[pypx] += 1                                       (lib :901)
+      s.nuis[o0 + n + r] = sp;
+      s.nuis_pos[o0 + n + r] = (int)(o0 + i);
+      s.mapO2[sp] += 1;  // mapO2[pypx] += 1                                     (lib :901)
     }
     n += tot;
     int tc;
@@ -157,28 +226,12 @@ __device__ __forceinline__ void pca_select_body(
     ncand += tc;
   }
   if (n == 0) {  // while len(pypx) > 0                                           (lib :899)
-    if (tid == 0) active[a] = 0, n_out[a] = 0, nb_out[a] = 0;
+    select_stop(s, a);
     return;
   }
   __syncthreads();
-  if (tid == 0) {
-    const int it = nbiter[a] + 1;  // nbiter += 1                                 (lib :900)
-    nbiter[a] = it;
-    s_ncand = it;
-  }
-  __syncthreads();
-  if (s_ncand > itermax) {  // if nbiter > itermax: nstop += 1; break          (lib :902-905)
-    if (tid == 0) {
-      atomicAdd(nstop, 1);
-      active[a] = 0;
-      n_out[a] = 0;
-      nb_out[a] = 0;
-    }
-    return;
-  }
-  // nb = 1 + int(len(nind) / Noise_population), clipped by the slice [:nb]     (lib :914-917)
-  int nb = 1 + (int)floor((double)ncand / noise_pop);
-  if (nb > ncand) nb = ncand;
+  if (select_itermax_stop(s, a, &s_it)) return;
+  const int nb = select_nb(ncand, s.noise_pop);
 
   if (nb > 0) {
     // ---- radix select of the nb-th smallest candidate (keys: bits of positive doubles)
@@ -197,31 +250,7 @@ __device__ __forceinline__ void pca_select_body(
         }
       }
       __syncthreads();
-      if (tid < 64) {  // wave 0: bucket holding rank `remaining` via a 64-lane prefix scan
-        const int rem0 = s_remaining;
-        const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2],
-                  h3 = hist[4 * tid + 3];
-        const int mine = h0 + h1 + h2 + h3;
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int v = __shfl_up(incl, off, 64);
-          if ((int)tid >= off) incl += v;
-        }
-        const int excl = incl - mine;
-        if (rem0 >= excl && rem0 < incl) {  // exactly one lane
-          int rem = rem0 - excl, b = 4 * tid;
-          if (rem >= h0) {
-            rem -= h0, ++b;
-            if (rem >= h1) {
-              rem -= h1, ++b;
-              if (rem >= h2) rem -= h2, ++b;
-            }
-          }
-          s_remaining = rem;
-          s_prefix = prefix | ((unsigned long long)b << shift);
-        }
-      }
+      if (tid < 64) select_pick_bucket(hist, prefix, shift, &s_remaining, &s_prefix, nullptr);
       maskbits |= 255ull << shift;
       __syncthreads();
     }
@@ -245,23 +274,15 @@ __device__ __forceinline__ void pca_select_body(
       const bool emit = cand && (key < tau || (eq && (neq + re) < need_equal));
       const int rm = scan.exclusive(emit, tm);
       if (emit) {
-        bg[o0 + nemit + rm] = sval(nfilt + rf);
-        bg_pos[o0 + nemit + rm] = (int)(o0 + nfilt + rf);
+        s.bg[o0 + nemit + rm] = s.spx[o0 + nfilt + rf];
+        s.bg_pos[o0 + nemit + rm] = (int)(o0 + nfilt + rf);
       }
       nfilt += tf;
       neq += te;
       nemit += tm;
     }
   }
-  if (tid == 0) {
-    nb_out[a] = nb;
-    if (n == 1) {  // if x_red.shape[1] == 1: break                              (lib :927-928)
-      active[a] = 0;
-      n_out[a] = 0;
-    } else {
-      n_out[a] = n;
-    }
-  }
+  select_finish(s, a, n, nb);
 }
 
 // Same selection for areas of at most 1024 * SEL_EPT spaxels (every 100 x 100 area), built for
@@ -296,13 +317,7 @@ __device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long 
   return pre + incl - v;
 }
 
-__device__ __forceinline__ void pca_select_fast_body(
-    const int *__restrict__ spx, const long *__restrict__ spx_off, const double *__restrict__ test,
-    const double *__restrict__ thr_, double noise_pop, int itermax, int *__restrict__ active,
-    int *__restrict__ nbiter, int *__restrict__ nstop, int *__restrict__ mapO2,
-    int *__restrict__ nuis, int *__restrict__ bg, int *__restrict__ nuis_pos,
-    int *__restrict__ bg_pos, int *__restrict__ n_out, int *__restrict__ nb_out,
-    uint8_t *__restrict__ inB, int *__restrict__ dlist, int *__restrict__ ndiff) {
+__device__ __forceinline__ void pca_select_fast_body(const SelectArgs &s) {
   __shared__ unsigned long long wsum[16], wmax[16];
   __shared__ unsigned bmap[1024 * SEL_EPT / 32];  // list positions emitted as background
   __shared__ int hist[256];
@@ -311,33 +326,33 @@ __device__ __forceinline__ void pca_select_fast_body(
   extern __shared__ int scache[];  // spaxel index of every list entry (for the filtered-index quirk)
   const int a = blockIdx.x;
   const int tid = threadIdx.x;
-  const long o0 = spx_off[a];
-  const int ns = (int)(spx_off[a + 1] - o0);
-  if (!active[a]) {
-    if (tid == 0) n_out[a] = 0, nb_out[a] = 0;
-    return;
-  }
-  const double thr = thr_[a];
+  const long o0 = s.spx_off[a];
+  const int ns = (int)(s.spx_off[a + 1] - o0);
+  if (!select_enter(s, a)) return;
+  const double thr = s.thr[a];
   const int E = (ns + 1023) / 1024;  // entries per thread (<= SEL_EPT)
   const int i0 = tid * E;
   // two batches of independent loads: indices, then values
   int sp[SEL_EPT];
   double tv[SEL_EPT];
 #pragma unroll
-  for (int e = 0; e < SEL_EPT; ++e) sp[e] = (e < E && i0 + e < ns) ? spx[o0 + i0 + e] : -1;
+  for (int e = 0; e < SEL_EPT; ++e) sp[e] = (e < E && i0 + e < ns) ? s.spx[o0 + i0 + e] : -1;
 #pragma unroll
-  for (int e = 0; e < SEL_EPT; ++e) tv[e] = sp[e] >= 0 ? test[sp[e]] : 0.0;
+  for (int e = 0; e < SEL_EPT; ++e) tv[e] = sp[e] >= 0 ? s.test[sp[e]] : 0.0;
 #pragma unroll
   for (int e = 0; e < SEL_EPT; ++e)
     if (sp[e] >= 0) scache[i0 + e] = sp[e];
   // membership of the previous iteration's background set (see the end of this function)
   unsigned oldmask = 0;
-  if (inB) {
+  {
     uint8_t ob[SEL_EPT];
 #pragma unroll
-    for (int e = 0; e < SEL_EPT; ++e) ob[e] = sp[e] >= 0 ? inB[o0 + i0 + e] : (uint8_t)0;
+    for (int e = 0; e < SEL_EPT; ++e) ob[e] = sp[e] >= 0 ? s.inB[o0 + i0 + e] : (uint8_t)0;
 #pragma unroll
     for (int e = 0; e < SEL_EPT; ++e) oldmask |= (unsigned)(ob[e] != 0) << e;
+    // (the mask is formed here: left to itself the compiler carries the loaded flags to the end
+    // of the kernel, twelve registers more than the 128 a block of 1024 threads has)
+    asm volatile("" : "+v"(oldmask));
     for (int i = tid; i < 1024 * SEL_EPT / 32; i += 1024) bmap[i] = 0u;
   }
 
@@ -353,7 +368,7 @@ __device__ __forceinline__ void pca_select_fast_body(
   const unsigned long long pre = block_scan_u64(cnt, wsum, tot);
   const int n = (int)(tot >> 40), ncand = (int)((tot >> 20) & 0xfffff);
   if (n == 0) {  // while len(pypx) > 0                                           (lib :899)
-    if (tid == 0) active[a] = 0, n_out[a] = 0, nb_out[a] = 0;
+    select_stop(s, a);
     return;
   }
   {  // nuisance compaction in index order (np.where(test > thr)); mapO2[pypx] += 1   (lib :901, before the itermax test)
@@ -361,30 +376,14 @@ __device__ __forceinline__ void pca_select_fast_body(
 #pragma unroll
     for (int e = 0; e < SEL_EPT; ++e)
       if (sp[e] >= 0 && tv[e] > thr) {
-        nuis[o0 + rn] = sp[e];
-        nuis_pos[o0 + rn] = (int)(o0 + i0 + e);
-        mapO2[sp[e]] += 1;
+        s.nuis[o0 + rn] = sp[e];
+        s.nuis_pos[o0 + rn] = (int)(o0 + i0 + e);
+        s.mapO2[sp[e]] += 1;
         ++rn;
       }
   }
-  if (tid == 0) {
-    const int it = nbiter[a] + 1;  // nbiter += 1                                 (lib :900)
-    nbiter[a] = it;
-    s_it = it;
-  }
-  __syncthreads();
-  if (s_it > itermax) {  // if nbiter > itermax: nstop += 1; break          (lib :902-905)
-    if (tid == 0) {
-      atomicAdd(nstop, 1);
-      active[a] = 0;
-      n_out[a] = 0;
-      nb_out[a] = 0;
-    }
-    return;
-  }
-  // nb = 1 + int(len(nind) / Noise_population), clipped by the slice [:nb]     (lib :914-917)
-  int nb = 1 + (int)floor((double)ncand / noise_pop);
-  if (nb > ncand) nb = ncand;
+  if (select_itermax_stop(s, a, &s_it)) return;
+  const int nb = select_nb(ncand, s.noise_pop);
 
   if (nb > 0) {
     // ---- radix select of the nb-th smallest candidate (keys: bits of positive doubles).
@@ -433,32 +432,7 @@ __device__ __forceinline__ void pca_select_fast_body(
           if ((key & above) == prefix) atomicAdd(&hist[(int)((unsigned)(key >> lo_bit) & dmask)], 1);
         }
       __syncthreads();
-      if (tid < 64) {  // wave 0: bucket holding rank `remaining` via a 64-lane prefix scan
-        const int rem0 = s_remaining;
-        const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2],
-                  h3 = hist[4 * tid + 3];
-        const int mine = h0 + h1 + h2 + h3;
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int v = __shfl_up(incl, off, 64);
-          if ((int)tid >= off) incl += v;
-        }
-        const int excl = incl - mine;
-        if (rem0 >= excl && rem0 < incl) {  // exactly one lane
-          int rem = rem0 - excl, b = 4 * tid, hb = h0;
-          if (rem >= h0) {
-            rem -= h0, ++b, hb = h1;
-            if (rem >= h1) {
-              rem -= h1, ++b, hb = h2;
-              if (rem >= h2) rem -= h2, ++b, hb = h3;
-            }
-          }
-          s_remaining = rem;
-          s_prefix = prefix | ((unsigned long long)b << lo_bit);
-          s_done = hb == 1;  // the bucket's only element is the answer (then rem == 0)
-        }
-      }
+      if (tid < 64) select_pick_bucket(hist, prefix, lo_bit, &s_remaining, &s_prefix, &s_done);
       __syncthreads();
       hi_bit = lo_bit;
       if (s_done) break;
@@ -501,9 +475,9 @@ __device__ __forceinline__ void pca_select_fast_body(
         const bool eq = key == tau;
         const bool emit = key < tau || (eq && eq_before < need_equal);
         if (emit) {
-          bg[o0 + emit_before] = scache[rp];
-          bg_pos[o0 + emit_before] = (int)(o0 + rp);
-          if (inB) atomicOr(&bmap[rp >> 5], 1u << (rp & 31));
+          s.bg[o0 + emit_before] = scache[rp];
+          s.bg_pos[o0 + emit_before] = (int)(o0 + rp);
+          atomicOr(&bmap[rp >> 5], 1u << (rp & 31));
           ++emit_before;
         }
         eq_before += eq;
@@ -511,80 +485,55 @@ __device__ __forceinline__ void pca_select_fast_body(
       ++rp;
     }
   }
-  if (inB) {
-    // The background set changes by a few columns per iteration (the O2 tests move slowly), so
-    // its mean is updated from the columns that entered or left it instead of re-gathered
-    // (bmean_kernel).  Here: the changes of membership in list order -- +(spaxel+1) entered,
-    // -(spaxel+1) left -- and the new membership flags.
-    __syncthreads();  // bmap complete
-    unsigned newmask = 0;
+  // The background set changes by a few columns per iteration (the O2 tests move slowly), so
+  // its mean is updated from the columns that entered or left it instead of re-gathered
+  // (bmean_kernel).  Here: the changes of membership in list order -- +(spaxel+1) entered,
+  // -(spaxel+1) left -- and the new membership flags.
+  __syncthreads();  // bmap complete
+  unsigned newmask = 0;
 #pragma unroll
-    for (int e = 0; e < SEL_EPT; ++e)
-      if (sp[e] >= 0) newmask |= ((bmap[(i0 + e) >> 5] >> ((i0 + e) & 31)) & 1u) << e;
-    const unsigned diff = newmask ^ oldmask;
-    unsigned long long tot3;
-    int r = (int)block_scan_u64((unsigned long long)__popc(diff), wsum, tot3);
+  for (int e = 0; e < SEL_EPT; ++e)
+    if (sp[e] >= 0) newmask |= ((bmap[(i0 + e) >> 5] >> ((i0 + e) & 31)) & 1u) << e;
+  const unsigned diff = newmask ^ oldmask;
+  unsigned long long tot3;
+  int r = (int)block_scan_u64((unsigned long long)__popc(diff), wsum, tot3);
 #pragma unroll
-    for (int e = 0; e < SEL_EPT; ++e)
-      if ((diff >> e) & 1u) {
-        const bool in = (newmask >> e) & 1u;
-        dlist[o0 + r++] = in ? sp[e] + 1 : -(sp[e] + 1);
-        inB[o0 + i0 + e] = (uint8_t)in;
-      }
-    if (tid == 0) ndiff[a] = (int)tot3;
-  }
-  if (tid == 0) {
-    nb_out[a] = nb;
-    if (n == 1) {  // if x_red.shape[1] == 1: break                              (lib :927-928)
-      active[a] = 0;
-      n_out[a] = 0;
-    } else {
-      n_out[a] = n;
+  for (int e = 0; e < SEL_EPT; ++e)
+    if ((diff >> e) & 1u) {
+      const bool in = (newmask >> e) & 1u;
+      s.dlist[o0 + r++] = in ? sp[e] + 1 : -(sp[e] + 1);
+      s.inB[o0 + i0 + e] = (uint8_t)in;
     }
-  }
+  if (tid == 0) s.ndiff[a] = (int)tot3;
+  select_finish(s, a, n, nb);
 }
 
 // The host sizes every launch of an iteration from n / nb of each area.  Instead of a D2H copy
 // and a stream synchronisation (~30 us of wake-up latency per iteration), each block stores its
 // two numbers straight into mapped, coherent host memory; the last block to finish (device
 // counter) raises the generation flag the host spins on.
-__device__ __forceinline__ void select_publish(int a, int na, const int *n_out, const int *nb_out,
-                                               int *host_out, unsigned *counter, int gen) {
+__device__ __forceinline__ void select_publish(const SelectArgs &s) {
   if (threadIdx.x != 0) return;
-  if (!host_out) return;
-  host_out[a] = n_out[a];
-  host_out[na + a] = nb_out[a];
+  if (!s.host_out) return;
+  const int a = blockIdx.x, na = gridDim.x;
+  s.host_out[a] = s.n_out[a];
+  s.host_out[na + a] = s.nb_out[a];
   __threadfence_system();
-  const unsigned old = atomicAdd(counter, 1u);
-  if (old + 1u == (unsigned)na * (unsigned)gen) {
+  const unsigned old = atomicAdd(s.counter, 1u);
+  if (old + 1u == (unsigned)na * (unsigned)s.gen) {
     __threadfence_system();
-    __hip_atomic_store(host_out + 2 * na, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(s.host_out + 2 * na, s.gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
-__global__ __launch_bounds__(1024) void pca_select_kernel(
-    const int *__restrict__ spx, const long *__restrict__ spx_off, const double *__restrict__ test,
-    const double *__restrict__ thr_, double noise_pop, int itermax, int *__restrict__ active,
-    int *__restrict__ nbiter, int *__restrict__ nstop, int *__restrict__ mapO2,
-    int *__restrict__ nuis, int *__restrict__ bg, int *__restrict__ nuis_pos,
-    int *__restrict__ bg_pos, int *__restrict__ n_out, int *__restrict__ nb_out, int lds_cap,
-    int *host_out, unsigned *counter, int gen) {
-  pca_select_body(spx, spx_off, test, thr_, noise_pop, itermax, active, nbiter, nstop, mapO2, nuis,
-                  bg, nuis_pos, bg_pos, n_out, nb_out, lds_cap);
-  select_publish(blockIdx.x, gridDim.x, n_out, nb_out, host_out, counter, gen);
+__global__ __launch_bounds__(1024) void pca_select_kernel(SelectArgs s) {
+  pca_select_body(s);
+  select_publish(s);
 }
 
-__global__ __launch_bounds__(1024) void pca_select_fast_kernel(
-    const int *__restrict__ spx, const long *__restrict__ spx_off, const double *__restrict__ test,
-    const double *__restrict__ thr_, double noise_pop, int itermax, int *__restrict__ active,
-    int *__restrict__ nbiter, int *__restrict__ nstop, int *__restrict__ mapO2,
-    int *__restrict__ nuis, int *__restrict__ bg, int *__restrict__ nuis_pos,
-    int *__restrict__ bg_pos, int *__restrict__ n_out, int *__restrict__ nb_out, int *host_out,
-    unsigned *counter, int gen, uint8_t *__restrict__ inB, int *__restrict__ dlist,
-    int *__restrict__ ndiff) {
-  pca_select_fast_body(spx, spx_off, test, thr_, noise_pop, itermax, active, nbiter, nstop, mapO2,
-                       nuis, bg, nuis_pos, bg_pos, n_out, nb_out, inB, dlist, ndiff);
-  select_publish(blockIdx.x, gridDim.x, n_out, nb_out, host_out, counter, gen);
+__global__ __launch_bounds__(1024) void pca_select_fast_kernel(SelectArgs s) {
+  pca_select_fast_body(s);
+  select_publish(s);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1265,6 +1214,11 @@ struct PcaRun {
   int *d_mapO2;
   int out_nx;  // > 0: d_F is a box inside a larger cube
   long out_py, out_pz;
+  const int nsmax_all;      // spaxels of the largest area
+  // Every area fits the register-resident selection (pca_select_fast_kernel).  Only that kernel
+  // keeps the changes of the background set, so it also decides whether bmean_kernel updates
+  // running sums (d_ssum, DF_SVALID) or gathers the background columns afresh.
+  const bool sel_resident;
 
   long ntot;                // list entries of all areas
   const float *src;         // where the not-yet-deflated cube is read from
@@ -1279,12 +1233,10 @@ struct PcaRun {
   int *d_nuis, *d_bg, *d_bg_pos, *d_npos[2];  // (nuisance positions: ping-pong)
   // Running sum of the background columns of each area (bmean_kernel): float64 [na][Nz], then
   // the signed list of columns that entered / left the set [ntot], their number per area [na]
-  // and the membership flag of every list position [ntot].  Only the register-resident
-  // selection kernel keeps them up to date.
+  // and the membership flag of every list position [ntot].  In use when sel_resident.
   double *d_ssum;
   int *d_dlist, *d_ndiff;
   uint8_t *d_inb;
-  bool use_delta;
   // spaxel -> (area, list position) for the kernel that walks the cube in memory order
   // (deflate_dot_rows_kernel); the per-iteration area -> work-list slot table travels with the
   // descriptors
@@ -1293,9 +1245,6 @@ struct PcaRun {
   double *d_U, *d_C;  // removed vectors U[area][z][PCA_CAP], coefficient rows C[PCA_CAP][list position]
   int *h_nnb;         // read-back [2*na] + [1] generation flag (mapped host memory)
   int *d_hostout;     // its device address
-  int nsmax_all;      // spaxels of the largest area
-  int sel_cap;        // LDS cache of pca_select_kernel (entries)
-  size_t sel_lds;
   int iters = 0;
   int gen = 1;  // selections launched so far + 1
   // host bookkeeping per area
@@ -1364,8 +1313,6 @@ int PcaRun::setup(const double *d_test0, const double *h_thr) {
   if ((rc = W.invert.reserve(ctx, (size_t)2 * S * sizeof(int)))) return rc;
   d_area_of = (int *)W.invert.p;
   d_pos_of = d_area_of + S;
-  nsmax_all = 0;
-  for (int a = 0; a < na; ++a) nsmax_all = std::max(nsmax_all, ns_of(a));
   ORIGIN_HIP(hipMemsetAsync(d_area_of, 0xFF, (size_t)S * sizeof(int), st));
   if (nsmax_all > 0)
     hipLaunchKernelGGL(invert_lists_kernel, dim3(cdiv(nsmax_all, 256), na), dim3(256), 0, st, d_spx,
@@ -1388,18 +1335,6 @@ int PcaRun::setup(const double *d_test0, const double *h_thr) {
   h_nnb = (int *)W.h_nnb.p;
   memset(h_nnb, 0, (size_t)(2 * na + 1) * sizeof(int));
   ORIGIN_HIP(hipHostGetDevicePointer((void **)&d_hostout, h_nnb, 0));
-
-  // LDS cache of the select kernel: the largest area, if it fits in 120 KiB
-  sel_cap = nsmax_all <= 12288 ? nsmax_all : 0;  // 12 B per spaxel: O2 value + spaxel index
-  sel_lds = (size_t)sel_cap * (sizeof(double) + sizeof(int));
-  if (sel_lds > 48 * 1024 &&
-      hipFuncSetAttribute((const void *)pca_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sel_lds) != hipSuccess) {
-    (void)hipGetLastError();
-    sel_cap = 0;
-    sel_lds = 0;
-  }
-  use_delta = nsmax_all <= 1024 * SEL_EPT;
   return ORIGIN_OK;
 }
 
@@ -1482,17 +1417,14 @@ int PcaRun::flush(bool final, bool only_done) {
 int PcaRun::select() {
   {
     ProfScope ps(ctx, K_PCA_SELECT, 2);
-    if (nsmax_all <= 1024 * SEL_EPT)
+    const SelectArgs sel{d_spx, d_spx_off, d_test, d_thr, noise_pop, itermax, d_active, d_nbiter,
+                         d_nstop, d_mapO2, d_nuis, d_bg, d_npos[iters & 1], d_bg_pos, d_n, d_nb,
+                         d_inb, d_dlist, d_ndiff, d_hostout, d_selcnt, gen};
+    if (sel_resident)  // dynamic LDS: the spaxel index of every list entry
       hipLaunchKernelGGL(pca_select_fast_kernel, dim3(na), dim3(1024),
-                         (size_t)nsmax_all * sizeof(int), st, d_spx, d_spx_off, d_test, d_thr,
-                         noise_pop, itermax, d_active, d_nbiter, d_nstop, d_mapO2, d_nuis, d_bg,
-                         d_npos[iters & 1], d_bg_pos, d_n, d_nb, d_hostout, d_selcnt, gen,
-                         use_delta ? d_inb : nullptr, d_dlist, d_ndiff);
+                         (size_t)nsmax_all * sizeof(int), st, sel);
     else
-      hipLaunchKernelGGL(pca_select_kernel, dim3(na), dim3(1024), sel_lds, st, d_spx, d_spx_off,
-                         d_test, d_thr, noise_pop, itermax, d_active, d_nbiter, d_nstop, d_mapO2,
-                         d_nuis, d_bg, d_npos[iters & 1], d_bg_pos, d_n, d_nb, sel_cap, d_hostout,
-                         d_selcnt, gen);
+      hipLaunchKernelGGL(pca_select_kernel, dim3(na), dim3(1024), 0, st, sel);
   }
   ORIGIN_LAUNCH_CHECK();
   int *flag = h_nnb + 2 * na;
@@ -1592,8 +1524,8 @@ int PcaRun::build_work_list(int nw, PcaWork &w, long *h_trace, int trace_cap) {
     D[(size_t)DF_FBOLD * nw + k] = have ? fb_off[a] : -1;
     D[(size_t)DF_LDOLD * nw + k] = fb_ld[a];
     D[(size_t)DF_NOLD * nw + k] = fb_n[a];
-    D[(size_t)DF_SVALID * nw + k] = use_delta && s_valid[a];
-    s_valid[a] = use_delta;  // this iteration's bmean_kernel leaves the sum behind
+    D[(size_t)DF_SVALID * nw + k] = sel_resident && s_valid[a];
+    s_valid[a] = sel_resident;  // this iteration's bmean_kernel leaves the sum behind
     w.xp += (long)Nz * ld;
     w.c += ld;
     w.g += (long)ld * ld;
@@ -1666,7 +1598,7 @@ int PcaRun::enqueue_chain(const PcaWork &w) {
     hipLaunchKernelGGL(cbar_kernel, dim3(nw), dim3(1024), 0, st, d_C, ntot, d_bg_pos, dD, nw,
                        d_cbar);
     hipLaunchKernelGGL(bmean_kernel, dim3(cdiv(Nz, 4), nw), dim3(64, 4), 0, st, src, Nz, S, d_bg,
-                       dD, nw, d_U, d_cbar, d_b, d_dlist, d_ndiff, use_delta ? d_ssum : nullptr);
+                       dD, nw, d_U, d_cbar, d_b, d_dlist, d_ndiff, sel_resident ? d_ssum : nullptr);
   }
   // z slices of the gather: enough blocks to fill the chip even when few areas iterate
   int nzb = (int)(((long)ctx->num_cu * 2 + (long)cdiv(w.ldmax, 64) * nw - 1) /
@@ -1702,9 +1634,10 @@ int PcaRun::enqueue_chain(const PcaWork &w) {
   }
   {
     ProfScope ps(ctx, K_PCA_EIG, 2);
-    if ((rc = origin_pca_eig_launch(ctx, nw, w.ldmax, d_G, dG, dLD, dN, (double *)W.part.p, dQ, d_v,
-                                    dC, d_info, all_small ? d_slab : nullptr, w.g, gram_ksplit,
-                                    debug ? d_info + (size_t)3 * nw : nullptr)))
+    const EigBatch batch{nw, d_G, dG, dLD, dN, (double *)W.part.p, dQ, d_v, dC, d_info,
+                         debug ? d_info + (size_t)3 * nw : nullptr};
+    const EigSlabs slabs = all_small ? EigSlabs{d_slab, w.g, gram_ksplit} : EigSlabs{};
+    if ((rc = origin_pca_eig_launch(ctx, batch, w.ldmax, slabs)))
       return rc;
   }
   if (debug && (rc = report_debug(nw, d_info))) return rc;
@@ -1865,8 +1798,12 @@ int origin_pca_run_into(origin_ctx *ctx, const float *d_X, float *d_F, int Nz, l
     ctx->pca_ws = new PcaWorkspace();
     ctx->pca_ws_free = [](void *p) { delete (PcaWorkspace *)p; };
   }
+  int nsmax_all = 0;
+  for (int a = 0; a < na; ++a)
+    nsmax_all = std::max(nsmax_all, (int)(h_spx_off[a + 1] - h_spx_off[a]));
   PcaRun R{ctx, *(PcaWorkspace *)ctx->pca_ws, st, d_X, d_F, Nz, S, na, d_spx, h_spx_off,
-           noise_pop, itermax, d_mapO2, out_nx, out_py, out_pz};
+           noise_pop, itermax, d_mapO2, out_nx, out_py, out_pz, nsmax_all,
+           nsmax_all <= 1024 * SEL_EPT};
   R.ntot = ntot;
   R.src = d_X;
   R.debug = getenv("ORIGIN_PCA_DEBUG") != nullptr;

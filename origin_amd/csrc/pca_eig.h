@@ -44,14 +44,29 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 constexpr int LANCZOS_M = 48;    // matrices of up to this many columns: the small-matrix solver
 constexpr int EIG_QROWS = 194;   // basis rows per matrix in the scratch d_q
 
-// Leading eigenvector of nmat symmetric PSD matrices on ctx->stream: matrix k is d_n[k] columns
-// at d_G + d_g_off[k] with row stride d_ld[k] (ldmax = the largest stride, which picks the
-// kernel), its vector goes to d_v + d_v_off[k], its basis scratch is EIG_QROWS * ld doubles at
-// d_q + d_q_off[k].  d_info (may be null): per matrix (theta, residual, restarts).  d_slab: the
-// K-split slabs of gram_kernel when every matrix has at most LANCZOS_M columns and the solver sums
-// them itself.  d_dbg (may be null): per matrix steps and time, then phase times.
-int origin_pca_eig_launch(origin_ctx *ctx, int nmat, long ldmax, const double *d_G,
-                          const long *d_g_off, const long *d_ld, const long *d_n, double *d_q,
-                          const long *d_q_off, double *d_v, const long *d_v_off, double *d_info,
-                          const double *d_slab = nullptr, long slab_stride = 0, int ksplit = 0,
-                          double *d_dbg = nullptr);
+// A batch of symmetric PSD matrices for the eigen-solver: matrix k is n[k] columns at G + g_off[k]
+// with row stride ld[k], its leading eigenvector goes to v + v_off[k], its basis scratch is
+// EIG_QROWS * ld[k] doubles at Q + q_off[k].  info (may be null): per matrix (theta, residual,
+// restarts).  dbg (may be null): per matrix steps and time, then phase times.
+struct EigBatch {
+  int nmat;
+  const double *G;
+  const long *g_off, *ld, *n;
+  double *Q;
+  const long *q_off;
+  double *v;
+  const long *v_off;
+  double *info, *dbg;
+};
+
+// The K-split slabs of gram_kernel (slab s of matrix k at ptr + s * stride + g_off[k]), given when
+// every matrix has at most LANCZOS_M columns: the solver then sums them itself instead of reading G.
+struct EigSlabs {
+  const double *ptr = nullptr;
+  long stride = 0;
+  int ksplit = 0;
+};
+
+// Leading eigenvector of every matrix of the batch, one launch on ctx->stream; ldmax = the largest
+// row stride, which picks the kernel (the size classes are listed at the top of pca_eig.hip).
+int origin_pca_eig_launch(origin_ctx *ctx, const EigBatch &batch, long ldmax, EigSlabs slabs = {});

@@ -1,6 +1,17 @@
 // Leading eigenvector of the Gram matrices of the greedy PCA (pca.hip): the device eigen-solvers
 // and the choice between them.  They take matrices and return vectors; nothing here knows the
 // PCA's work list.
+//
+// One launch solves a batch (EigBatch, pca_eig.h), one block per matrix.  The largest row stride of
+// the batch, ldmax, picks the kernel (eig_dispatch); inside it every block picks by its own n:
+//   ldmax <= PW_N, or slabs given   eig_power_kernel       1024 threads   the power solvers only
+//   ldmax <= LP_NMAX                lanczos_plain_kernel    512 threads   power solvers, else plain
+//                                                                         Lanczos with G on the CU
+//   ldmax >  LP_NMAX                lanczos_kernel         1024 threads   power solvers, else
+//                                                                         restarted Lanczos
+// The power solvers (eig_power_front): n <= LANCZOS_M repeated squaring of the matrix in LDS
+// (eig_small_power, also summing the K-split slabs of gram_kernel when they are given), n <= PW_N
+// the same with both buffers in dynamic LDS (eig_mid_power).
 #include <algorithm>
 #include <vector>
 
@@ -9,183 +20,15 @@
 
 namespace {
 
-// ------------------------------------------------------------------------------------
-// Leading eigenvector of the symmetric PSD matrix G (n x n, row stride ld): restarted
-// Lanczos with full (twice-applied classical Gram-Schmidt) re-orthogonalisation.  One block
-// of 1024 threads per matrix; the Krylov basis Q lives in global scratch (L2 resident).
-// The small tridiagonal problem is solved by 64-way multisection on Sturm counts (wave 0)
-// and inverse iteration with partial pivoting (thread 0).
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double *red) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) t += red[w];
-  return t;
-}
-
-// Number of eigenvalues < x of the symmetric tridiagonal with diagonal a[0..m) and squared
-// off-diagonals bb[0..m-1), both already divided by the norm of T (so |a - x| <= 3, bb <= 1):
-// sign changes of the leading principal minors p_i = (a_i - x) p_{i-1} - bb_{i-1} p_{i-2}.
-// One multiply-add on the dependency chain per row (the pivot form q_i = a_i - x - bb/q_{i-1}
-// carries a float64 division, ~15 dependent instructions).  A minor that is exactly zero takes
-// the sign opposite to its predecessor -- the same convention as replacing a zero pivot by a
-// tiny negative one.  With the scaling the minors cannot overflow for m <= 48; they are
-// rescaled every 8 rows against underflow.
-// The rows are taken eight at a time with their coefficients loaded up front (the loads do not
-// depend on the chain); the arrays are padded by 8 and rows >= m are not counted.
+// Work area of the tridiagonal solvers (tridiag_top_lean, tridiag_top_fast), padded behind the
+// largest m so that the serial recurrences can load a few rows ahead without bounds tests.
 constexpr int TRI_PAD = LANCZOS_M + 8;
-__device__ __forceinline__ int sturm_count(const double *a, const double *bb, int m, double x) {
-  double p0 = 1.0, p1 = a[0] - x;
-  bool s1 = p1 < 0.0 || p1 == 0.0;  // sign of p_{i-1} (true: negative), p_{-1} = 1
-  int cnt = s1;
-  for (int i0 = 0; i0 < m - 1; i0 += 8) {
-    double av[8], bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) av[e] = a[i0 + 1 + e] - x, bv[e] = bb[i0 + e];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const double p2 = fma(av[e], p1, -bv[e] * p0);
-      const bool s2 = p2 < 0.0 || (p2 == 0.0 && !s1);
-      cnt += (i0 + 1 + e < m) && (s2 != s1);
-      p0 = p1, p1 = p2, s1 = s2;
-    }
-    if (fabs(p1) < 1e-100 && fabs(p0) < 1e-100) p0 *= 1e100, p1 *= 1e100;
-  }
-  return cnt;
-}
-
-// Largest eigenpair of the symmetric tridiagonal T (alpha[0..m), beta[0..m-1)), executed by
-// ONE wave: 64-way multisection on Sturm counts for the eigenvalue, then two steps of inverse
-// iteration (lane 0) for the unit eigenvector, left in ws.x.  Returns the eigenvalue.
-// The shift of the inverse iteration lies just above the largest eigenvalue, so T - sigma I is
-// negative definite and its LDL^T factorisation needs no pivoting; it is formed once, with the
-// pivot reciprocals kept for both solves.
 template <int PAD_>
 struct TriWorkT {
   static constexpr int PAD = PAD_;
   double x[PAD_], a[PAD_], bb[PAD_], l[PAD_], rd[PAD_];
 };
 typedef TriWorkT<TRI_PAD> TriWork;
-
-__device__ __forceinline__ double tridiag_top(const double *alpha, const double *beta, int m,
-                                              int lane, TriWork &ws) {
-  double lo = 1e300, hi = -1e300, tn = 0.0;
-  for (int i = 0; i < m; ++i) {
-    const double r = (i > 0 ? fabs(beta[i - 1]) : 0.0) + (i < m - 1 ? fabs(beta[i]) : 0.0);
-    lo = fmin(lo, alpha[i] - r);
-    hi = fmax(hi, alpha[i] + r);
-    tn = fmax(tn, fabs(alpha[i]) + r);
-  }
-  if (!(tn > 0.0)) {  // T == 0
-    if (lane == 0)
-      for (int i = 0; i < m; ++i) ws.x[i] = i == 0 ? 1.0 : 0.0;
-    return 0.0;
-  }
-  // scaled copy: a = alpha / tn, bb = (beta / tn)^2
-  const double itn = 1.0 / tn;
-  for (int i = lane; i < m; i += 64) {
-    ws.a[i] = alpha[i] * itn;
-    const double b = i < m - 1 ? beta[i] * itn : 0.0;
-    ws.bb[i] = b * b;
-  }
-  lo *= itn;
-  hi = hi * itn + 1e-14;
-  for (int it = 0; it < 10; ++it) {  // 65^10 > 2^53 * (hi - lo)
-    // lane l tests x_l = lo + (l+1) (hi-lo)/65 ; count(x) == m  <=>  x > theta_max
-    const double x = lo + (hi - lo) * (double)(lane + 1) / 65.0;
-    const bool above = sturm_count(ws.a, ws.bb, m, x) >= m;
-    const unsigned long long bal = __ballot(above);
-    const int first = bal ? __ffsll((long long)bal) - 1 : 64;  // first lane above
-    const double nlo = first == 0 ? lo : lo + (hi - lo) * (double)first / 65.0;
-    const double nhi = first == 64 ? hi : lo + (hi - lo) * (double)(first + 1) / 65.0;
-    lo = nlo;
-    hi = nhi;
-  }
-  const double theta_s = 0.5 * (lo + hi);  // in units of tn
-  if (lane == 0) {
-    double *x = ws.x, *l = ws.l, *rd = ws.rd;
-    const double sigma = theta_s + 4e-16;
-    // LDL^T of (T - sigma I) / tn:  d_0 = a_0 - sigma, l_i = b_i / d_i,
-    // d_{i+1} = a_{i+1} - sigma - b_i^2 / d_i   (all d < 0; a pivot that rounding pushed to
-    // zero or above is replaced by a tiny negative one).  Every loop below is a serial
-    // recurrence: eight rows at a time, operands loaded before and results stored after the
-    // chain, so that an LDS round trip is paid per eight rows instead of per row.
-    double d = ws.a[0] - sigma;
-    for (int i0 = 0; i0 < m; i0 += 8) {
-      double an[8], bq[8], bl[8], rr[8], ll[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        an[e] = ws.a[i0 + e + 1] - sigma;  // row i0 + e + 1 (padding beyond m: unused)
-        bq[e] = ws.bb[i0 + e];
-        bl[e] = i0 + e < m - 1 ? beta[i0 + e] * itn : 0.0;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (!(d < -1e-30)) d = -1e-30;
-        const double r = 1.0 / d;
-        rr[e] = r;
-        ll[e] = bl[e] * r;
-        d = an[e] - bq[e] * r;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) rd[i0 + e] = rr[e], l[i0 + e] = ll[e];
-    }
-    // rows >= m of l / rd hold padding values: the solves below never use them
-    const double x0 = 1.0 / sqrt((double)m);
-    for (int i = 0; i < TRI_PAD; ++i) x[i] = i < m ? x0 : 0.0;
-    for (int iter = 0; iter < 2; ++iter) {
-      // L y = x   (y_0 = x_0, y_i = x_i - l_{i-1} y_{i-1})
-      double y = x[0];
-      for (int i0 = 1; i0 < m; i0 += 8) {
-        double lv[8], xv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) lv[e] = l[i0 + e - 1], xv[e] = x[i0 + e];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          y = fma(-lv[e], y, xv[e]);
-          xv[e] = y;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (i0 + e < m) x[i0 + e] = xv[e];
-      }
-      // D z = y ; L^T w = z   (w_{m-1} = y_{m-1} / d_{m-1}, w_i = y_i / d_i - l_i w_{i+1})
-      double w = 0.0, nx = 0.0;
-      for (int i0 = (m - 1) & ~7; i0 >= 0; i0 -= 8) {
-        double lv[8], zv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const bool in = i0 + e < m;
-          lv[e] = (i0 + e < m - 1) ? l[i0 + e] : 0.0;
-          zv[e] = in ? x[i0 + e] * rd[i0 + e] : 0.0;
-        }
-#pragma unroll
-        for (int e = 7; e >= 0; --e) {
-          w = fma(-lv[e], w, zv[e]);  // rows >= m: lv = zv = 0 keep w = 0
-          zv[e] = w;
-          nx = fma(w, w, nx);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (i0 + e < m) x[i0 + e] = zv[e];
-      }
-      nx = 1.0 / sqrt(nx);
-      for (int i0 = 0; i0 < m; i0 += 8) {
-        double xv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) xv[e] = x[i0 + e] * nx;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (i0 + e < m) x[i0 + e] = xv[e];
-      }
-    }
-  }
-  return theta_s * tn;
-}
 
 // Work area of the small-matrix solver (n <= LANCZOS_M), in dynamic LDS, zeroed by the kernel.
 struct SmallWork {
@@ -203,7 +46,7 @@ struct SmallWork {
 // tridiagonal eigen-solve, took 50-70 us for n = 20 where this takes about 15).  All 1024 threads of the block take part; sw.G holds the matrix
 // (zero beyond n) and is kept for the residual.  B_k is symmetric by construction (both
 // operands are read as rows k of B_{k-1}: B^T B).
-// NW: waves of the calling block (16 in lanczos_kernel, 8 in lanczos_plain_kernel).
+// NW: waves of the calling block (8 in lanczos_plain_kernel, 16 in the other two).
 template <int NW>
 __device__ void eig_small_power(int n, int ld, SmallWork &sw, double *__restrict__ v, double *info3) {
   __shared__ double s_tr, s_part[4];
@@ -427,241 +270,71 @@ __device__ void eig_mid_power(const double *__restrict__ Gk, int n, int ld, doub
   }
 }
 
-// QLDS: the Krylov basis (LANCZOS_M + 2 rows of length ld) lives in dynamic LDS instead of global
-// memory -- the Gram-Schmidt passes of this one-block kernel are chains of dependent reads, and
-// an L2 round trip costs ~0.7 us against ~0.05 us for LDS.  The host picks it when the basis of
-// the largest matrix of the launch fits (ld <= LANCZOS_QLDS_LD).
-constexpr int LANCZOS_QLDS_LD = 368;  // (48 + 2) * 368 * 8 B = 147 KB
-template <bool QLDS>
-__global__ __launch_bounds__(1024) void lanczos_kernel(const double *__restrict__ G,
-                                                       const long *__restrict__ g_off,
-                                                       const long *__restrict__ ld_,
-                                                       const long *__restrict__ n_,
-                                                       double *__restrict__ Q,
-                                                       const long *__restrict__ q_off,
-                                                       double *__restrict__ vout,
-                                                       const long *__restrict__ v_off,
-                                                       int max_restart, double tol,
-                                                       double *__restrict__ info,
-                                                       const double *__restrict__ slab,
-                                                       long slab_stride, int ksplit,
-                                                       int power_nmax,
-                                                       double *__restrict__ dbg = nullptr) {
-  __shared__ double alpha[LANCZOS_M], beta[LANCZOS_M], h[LANCZOS_M + 1];
-  __shared__ TriWork ws;
-  __shared__ double red[16];
-  __shared__ double upd[4][256];
-  __shared__ double s_theta;
-  extern __shared__ __align__(16) double lz_dyn[];  // SmallWork, or the basis when QLDS
-  double *svec = ws.x;
-  const int k = blockIdx.x;
-  const int n = (int)n_[k], ld = (int)ld_[k];
-  if (n < 1) return;  // (n == 1 is a valid 1 x 1 problem for origin_pca_eig; the PCA loop never
-                      // sends fewer than two columns except for areas that have just finished)
-  const unsigned long long t_dbg = dbg ? wall_clock64() : 0ull;  // 100 MHz
-  int steps_dbg = 0;
-  const double *Gk = G + g_off[k];
-  double *Qk;  // (LANCZOS_M + 2) rows of length ld; last row = Ritz vector
-  if constexpr (QLDS) Qk = lz_dyn;
-  else Qk = Q + q_off[k];
-  double *y = Qk + (long)(LANCZOS_M + 1) * ld;
-  double *v = vout + v_off[k];
+// The power solvers in front of every kernel: a block whose matrix has at most PW_N columns is
+// solved here and the caller returns.  n <= LANCZOS_M: SmallWork at the start of the dynamic LDS,
+// zeroed, G loaded into it -- from the K-split slabs of gram_kernel when they are given (16 waves
+// only: the reduction kernel is skipped when every matrix of the launch is small) -- and
+// eig_small_power; n <= PW_N: eig_mid_power.  dbg gets the step codes -1 / -2 and the time.
+// NW: waves of the calling block.  Returns whether the block is done (also for an empty slot).
+template <int NW>
+__device__ __forceinline__ bool eig_power_front(const EigBatch &b, const EigSlabs &slabs, int k,
+                                                double *lds) {
+  const int n = (int)b.n[k], ld = (int)b.ld[k];
+  if (n < 1) return true;  // (n == 1 is a valid 1 x 1 problem for origin_pca_eig; the PCA loop never
+                           // sends fewer than two columns except for areas that have just finished)
+  if (n > PW_N) return false;
+  const unsigned long long t_dbg = b.dbg ? wall_clock64() : 0ull;  // 100 MHz
+  const double *Gk = b.G + b.g_off[k];
+  double *v = b.v + b.v_off[k];
+  double *info3 = b.info ? b.info + 3 * k : nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (n <= LANCZOS_M) {  // small matrix: repeated squaring on the matrix cores (eig_small_power)
-    SmallWork &sw = *reinterpret_cast<SmallWork *>(lz_dyn);
+    SmallWork &sw = *reinterpret_cast<SmallWork *>(lds);
     {  // the solver relies on zeros beyond n
       double *z8 = reinterpret_cast<double *>(&sw);
-      for (int i = tid; i < (int)(sizeof(SmallWork) / sizeof(double)); i += 1024) z8[i] = 0.0;
+      for (int i = tid; i < (int)(sizeof(SmallWork) / sizeof(double)); i += 64 * NW) z8[i] = 0.0;
       __syncthreads();
     }
-    if (slab) {
-      // G straight from the K-split slabs of gram_kernel (the reduction kernel is skipped when
-      // every matrix of the launch is small): same sums, in the same order, as
+    if (NW == 16 && slabs.ptr) {
+      // G straight from the K-split slabs of gram_kernel: same sums, in the same order, as
       // gram_reduce_kernel.  Only tiles (ti <= tj) exist: the lower-left one is read mirrored.
       // All 16 waves share the rows; the <= 32 slab values of an element are independent loads
       // (one L2 round trip), summed in slab order.
-      const double *sk = slab + g_off[k];
+      const double *sk = slabs.ptr + b.g_off[k];
       for (int c = wave; c < n; c += 16) {
         if (lane < n) {
           const bool up = (c >> 5) <= (lane >> 5);
           const long off = up ? (long)c * ld + lane : (long)lane * ld + c;
           double part[32];
 #pragma unroll
-          for (int ks = 0; ks < 32; ++ks) part[ks] = ks < ksplit ? sk[(long)ks * slab_stride + off] : 0.0;
+          for (int ks = 0; ks < 32; ++ks)
+            part[ks] = ks < slabs.ksplit ? sk[(long)ks * slabs.stride + off] : 0.0;
           double acc = 0.0;
 #pragma unroll
           for (int ks = 0; ks < 32; ++ks) acc += part[ks];  // trailing zeros do not change the sum
           sw.G[c][lane] = acc;
         }
       }
-      __syncthreads();
-    }
-    else {
-      for (int c = wave; c < n; c += 16)
+    } else {
+      for (int c = wave; c < n; c += NW)
         if (lane < n) sw.G[c][lane] = Gk[(long)c * ld + lane];
-      __syncthreads();
     }
-    eig_small_power<16>(n, ld, sw, v, info ? info + 3 * k : nullptr);
-    if (dbg && threadIdx.x == 0) dbg[2 * k] = -1.0, dbg[2 * k + 1] = (double)(wall_clock64() - t_dbg) * 0.01;
-    return;
+    __syncthreads();
+    eig_small_power<NW>(n, ld, sw, v, info3);
+  } else {  // mid-size matrix: repeated squaring with both buffers in LDS
+    eig_mid_power<NW>(Gk, n, ld, lds, v, info3);
   }
-  if (n <= power_nmax) {  // mid-size matrix: repeated squaring with both buffers in LDS
-    eig_mid_power<16>(Gk, n, ld, lz_dyn, v, info ? info + 3 * k : nullptr);
-    if (dbg && threadIdx.x == 0) dbg[2 * k] = -2.0, dbg[2 * k + 1] = (double)(wall_clock64() - t_dbg) * 0.01;
-    return;
+  if (b.dbg && tid == 0) {
+    b.dbg[2 * k] = n <= LANCZOS_M ? -1.0 : -2.0;
+    b.dbg[2 * k + 1] = (double)(wall_clock64() - t_dbg) * 0.01;
   }
-  const int mfull = min(LANCZOS_M, n);
+  return true;
+}
 
-  // start vector: G * ones (a few power-like steps come for free in the Krylov space)
-  for (int r = wave; r < n; r += 16) {
-    double acc = 0.0;
-    for (int c = lane; c < n; c += 64) acc += Gk[(long)r * ld + c];
-    acc = wave_sum_d(acc);
-    if (lane == 0) y[r] = acc;
-  }
-  __syncthreads();
-  double theta = 0.0, resid = 0.0;
-  int restarts = 0;
-  for (; restarts < max_restart; ++restarts) {
-    // q_0 = y / |y|
-    double p = 0.0;
-    for (int e = tid; e < n; e += 1024) p = fma(y[e], y[e], p);
-    const double nrm = sqrt(block_sum(p, red));
-    const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-    for (int e = tid; e < n; e += 1024) Qk[e] = (nrm > 0.0) ? y[e] * inv : (e == 0 ? 1.0 : 0.0);
-    __syncthreads();
-    int m = 0;
-    double beta_last = 0.0;
-    // a dominant nuisance converges in a few steps: the Ritz pair is tested at LANCZOS_M/2
-    // and 3/4 LANCZOS_M, and the recurrence goes on from there (no restart) when it fails
-    const int mmax = mfull;
-    bool solved = false;
-    for (int j = 0; j < mmax; ++j) {
-      const double *qj = Qk + (long)j * ld;
-      double *w = Qk + (long)(j + 1) * ld;
-      // w = G q_j.  G is symmetric: thread r accumulates sum_c G[c][r] q_j[c], so that lanes
-      // read consecutive addresses and no cross-lane reduction is needed; the columns are
-      // split over 4 groups of 256 threads and combined through LDS.
-      {
-        const int part = tid >> 8, r0 = tid & 255;
-        for (int rb = 0; rb < n; rb += 256) {
-          const int r = rb + r0;
-          double acc = 0.0;
-          if (r < n) {
-            // G comes from L2 (~0.7 us per round trip): 16 loads per lane in flight
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-            int c = part;
-            for (; c + 60 < n; c += 64) {
-              double g[16];
-#pragma unroll
-              for (int q = 0; q < 16; ++q) g[q] = Gk[(long)(c + 4 * q) * ld + r];
-#pragma unroll
-              for (int q = 0; q < 16; q += 4) {
-                a0 = fma(g[q], qj[c + 4 * q], a0);
-                a1 = fma(g[q + 1], qj[c + 4 * q + 4], a1);
-                a2 = fma(g[q + 2], qj[c + 4 * q + 8], a2);
-                a3 = fma(g[q + 3], qj[c + 4 * q + 12], a3);
-              }
-            }
-            for (; c < n; c += 4) a0 = fma(Gk[(long)c * ld + r], qj[c], a0);
-            acc = (a0 + a1) + (a2 + a3);
-          }
-          upd[part][r0] = acc;
-          __syncthreads();
-          if (part == 0 && r < n) w[r] = (upd[0][r0] + upd[1][r0]) + (upd[2][r0] + upd[3][r0]);
-          __syncthreads();
-        }
-      }
-      // classical Gram-Schmidt against q_0..q_j, twice; alpha_j = first-pass h_j (+ fix)
-      double aj = 0.0;
-      for (int pass = 0; pass < 2; ++pass) {
-        for (int i = wave; i <= j; i += 16) {
-          const double *qi = Qk + (long)i * ld;
-          double acc = 0.0;
-#pragma unroll 4
-          for (int c = lane; c < n; c += 64) acc = fma(qi[c], w[c], acc);
-          acc = wave_sum_d(acc);
-          if (lane == 0) h[i] = acc;
-        }
-        __syncthreads();
-        aj += h[j];
-        // w -= Q h with the j+1 rows split over 4 thread groups (independent loads in
-        // flight instead of one dependent chain per element), combined through LDS
-        {
-          const int part = tid >> 8, e0 = tid & 255;
-          for (int eb = 0; eb < n; eb += 256) {
-            const int e = eb + e0;
-            double acc = 0.0;
-            if (e < n) {
-#pragma unroll 4
-              for (int i = part; i <= j; i += 4) acc = fma(h[i], Qk[(long)i * ld + e], acc);
-            }
-            upd[part][e0] = acc;
-            __syncthreads();
-            if (part == 0 && e < n)
-              w[e] -= (upd[0][e0] + upd[1][e0]) + (upd[2][e0] + upd[3][e0]);
-            __syncthreads();
-          }
-        }
-      }
-      double pw = 0.0;
-      for (int e = tid; e < n; e += 1024) pw = fma(w[e], w[e], pw);
-      const double bj = sqrt(block_sum(pw, red));
-      if (tid == 0) alpha[j] = aj, beta[j] = bj;
-      m = j + 1;
-      beta_last = bj;
-      // invariant subspace reached (also the exact case m == n)
-      if (bj <= 1e-300 || bj <= 1e-15 * fabs(aj)) break;
-      if (j + 1 < mmax) {
-        const double ib = 1.0 / bj;
-        for (int e = tid; e < n; e += 1024) w[e] *= ib;
-      }
-      __syncthreads();
-      if (j + 1 < mmax && (j + 1 == LANCZOS_M / 2 || j + 1 == 3 * LANCZOS_M / 4)) {
-        if (wave == 0) {
-          const double th = tridiag_top(alpha, beta, m, lane, ws);
-          if (lane == 0) s_theta = th;
-        }
-        __syncthreads();
-        solved = fabs(bj * svec[m - 1]) <= tol * fabs(s_theta);  // block-uniform
-        if (solved) break;
-      }
-    }
-    __syncthreads();
-    // ---- largest eigenpair of T_m (wave 0)
-    if (!solved) {
-      if (wave == 0) {
-        const double th = tridiag_top(alpha, beta, m, lane, ws);
-        if (lane == 0) s_theta = th;
-      }
-      __syncthreads();
-    }
-    theta = s_theta;
-    // y = Q s
-    for (int e = tid; e < n; e += 1024) {
-      double acc = 0.0;
-#pragma unroll 8
-      for (int i = 0; i < m; ++i) acc = fma(svec[i], Qk[(long)i * ld + e], acc);
-      y[e] = acc;
-    }
-    resid = fabs(beta_last * svec[m - 1]);
-    steps_dbg += m;
-    __syncthreads();
-    if (m >= n || resid <= tol * fabs(theta)) break;
-  }
-  // final normalisation of the eigenvector
-  double p = 0.0;
-  for (int e = tid; e < n; e += 1024) p = fma(y[e], y[e], p);
-  const double nrm = sqrt(block_sum(p, red));
-  const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-  for (int e = tid; e < n; e += 1024) v[e] = y[e] * inv;
-  for (int e = n + tid; e < ld; e += 1024) v[e] = 0.0;
-  if (tid == 0 && info) {
-    info[3 * k] = theta;
-    info[3 * k + 1] = resid;
-    info[3 * k + 2] = (double)restarts;
-  }
-  if (tid == 0 && dbg) dbg[2 * k] = (double)steps_dbg, dbg[2 * k + 1] = (double)(wall_clock64() - t_dbg) * 0.01;
+// Launches whose largest matrix has at most PW_N columns, and the all-small slab launch.
+__global__ __launch_bounds__(1024) void eig_power_kernel(EigBatch b, EigSlabs slabs) {
+  extern __shared__ __align__(16) double lz_dyn[];  // SmallWork, or the squaring buffers
+  eig_power_front<16>(b, slabs, blockIdx.x, lz_dyn);
 }
 
 // ------------------------------------------------------------------------------------
@@ -711,11 +384,15 @@ struct PlainLds {  // carved from the dynamic LDS of the block
 constexpr size_t LP_BYTES = sizeof(PlainLds);
 static_assert(LP_BYTES <= 156 * 1024, "plain Lanczos work area must fit the CU's LDS");
 
-// The tridiagonal solver of lanczos_kernel with a small register footprint (the matrix sits in
-// registers next to it): bounds and every row-independent quantity are computed lane-parallel,
-// the serial recurrences (Sturm chains, pivots of the LDL^T factorisation, the two triangular
-// solves) walk four rows per LDS round trip.  Same algorithm, same results to rounding; any m
-// up to the padded size of the work area.
+// Number of eigenvalues < x of the symmetric tridiagonal with diagonal a[0..m) and squared
+// off-diagonals bb[0..m-1), both already divided by the norm of T (so |a - x| <= 3, bb <= 1):
+// sign changes of the leading principal minors p_i = (a_i - x) p_{i-1} - bb_{i-1} p_{i-2}.
+// One multiply-add on the dependency chain per row (the pivot form q_i = a_i - x - bb/q_{i-1}
+// carries a float64 division, ~15 dependent instructions).  A minor that is exactly zero takes
+// the sign opposite to its predecessor -- the same convention as replacing a zero pivot by a
+// tiny negative one.  The minors are rescaled every 4 rows against under- and overflow.
+// The rows are taken four at a time with their coefficients loaded up front (the loads do not
+// depend on the chain); the arrays are padded and rows >= m are not counted.
 __device__ __forceinline__ int sturm_count4(const double *a, const double *bb, int m, double x) {
   double p0 = 1.0, p1 = a[0] - x;
   bool s1 = p1 < 0.0 || p1 == 0.0;
@@ -743,6 +420,16 @@ __device__ __forceinline__ double wave_max_d(double v) {
   return v;
 }
 
+// Largest eigenpair of the symmetric tridiagonal T (alpha[0..m), beta[0..m-1)), executed by
+// ONE wave: 64-way multisection on Sturm counts for the eigenvalue, then two steps of inverse
+// iteration for the unit eigenvector, left in ws.x.  Returns the eigenvalue.
+// The shift of the inverse iteration lies just above the largest eigenvalue, so T - sigma I is
+// negative definite and its LDL^T factorisation needs no pivoting; it is formed once, with the
+// pivot reciprocals kept for both solves.
+// Small register footprint (in lanczos_plain the matrix sits in registers next to it): bounds and
+// every row-independent quantity are computed lane-parallel, the serial recurrences (Sturm chains,
+// pivots of the LDL^T factorisation, the two triangular solves) walk four rows per LDS round
+// trip in lane 0.  Any m up to the padded size of the work area.
 template <class TW>
 __device__ __forceinline__ double tridiag_top_lean(const double *alpha, const double *beta, int m,
                                                    int lane, TW &ws) {
@@ -887,7 +574,7 @@ struct TriRegs {
 // v_alignbit that shifts the sign bit of p_i into a 32-bit history; the changes are counted per
 // 31 rows (popcount of history ^ history >> 1).  A minor that is exactly zero counts as positive:
 // the next one, -bb p_{i-2}, then has the sign opposite to p_{i-2}, which gives the same number
-// of changes as the "zero takes the sign opposite to its predecessor" rule of sturm_count for
+// of changes as the "zero takes the sign opposite to its predecessor" rule of sturm_count4 for
 // every interior row, and makes the count that of the eigenvalues strictly below x.
 __device__ __forceinline__ int sturm_count_rl(const TriRegs &t, int m, double x) {
   // hist: the signs of the last `held` minors, newest at bit 0; starts with p_{-1} = 1
@@ -1333,97 +1020,256 @@ __device__ void lanczos_plain(const double *__restrict__ Gk, int n, int ld, doub
   *steps_out = steps;
 }
 
-__global__ __launch_bounds__(LP_NT) void lanczos_plain_kernel(
-    const double *__restrict__ G, const long *__restrict__ g_off, const long *__restrict__ ld_,
-    const long *__restrict__ n_, double *__restrict__ Q, const long *__restrict__ q_off,
-    double *__restrict__ vout, const long *__restrict__ v_off, int max_restart, double tol,
-    double *__restrict__ info, double *__restrict__ dbg) {
+__global__ __launch_bounds__(LP_NT) void lanczos_plain_kernel(EigBatch b, int max_restart, double tol) {
   extern __shared__ __align__(16) double lz_dyn[];  // SmallWork, the squaring buffers, or PlainLds
   const int k = blockIdx.x;
-  const int n = (int)n_[k], ld = (int)ld_[k];
-  if (n < 1) return;
+  if (eig_power_front<LP_NW>(b, EigSlabs(), k, lz_dyn)) return;
+  const int n = (int)b.n[k], ld = (int)b.ld[k];
+  double *const dbg = b.dbg;
   const unsigned long long t_dbg = dbg ? wall_clock64() : 0ull;
-  const double *Gk = G + g_off[k];
-  double *v = vout + v_off[k];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int steps = 0;
-  if (n <= LANCZOS_M) {
-    SmallWork &sw = *reinterpret_cast<SmallWork *>(lz_dyn);
-    double *z8 = reinterpret_cast<double *>(&sw);
-    for (int i = tid; i < (int)(sizeof(SmallWork) / sizeof(double)); i += LP_NT) z8[i] = 0.0;
-    __syncthreads();
-    for (int c = wave; c < n; c += LP_NW)
-      if (lane < n) sw.G[c][lane] = Gk[(long)c * ld + lane];
-    __syncthreads();
-    eig_small_power<LP_NW>(n, ld, sw, v, info ? info + 3 * k : nullptr);
-    steps = -1;
-  } else if (n <= PW_N) {
-    eig_mid_power<LP_NW>(Gk, n, ld, lz_dyn, v, info ? info + 3 * k : nullptr);
-    steps = -2;
-  } else {
-    PlainLds &L = *reinterpret_cast<PlainLds *>(lz_dyn);
-    double *Vk = Q + q_off[k];
-    double *tph = dbg ? dbg + 2 * (long)gridDim.x + 8 * (long)k : nullptr;
-    if (tph && tid == 0)
-      for (int e = 0; e < 8; ++e) tph[e] = 0.0;
-    if (n <= 256)
-      lanczos_plain<1>(Gk, n, ld, Vk, v, L, max_restart, tol, info ? info + 3 * k : nullptr, &steps,
-                       tph);
-    else
-      lanczos_plain<2>(Gk, n, ld, Vk, v, L, max_restart, tol, info ? info + 3 * k : nullptr, &steps,
-                       tph);
-  }
+  PlainLds &L = *reinterpret_cast<PlainLds *>(lz_dyn);
+  const double *Gk = b.G + b.g_off[k];
+  double *Vk = b.Q + b.q_off[k], *v = b.v + b.v_off[k];
+  double *info3 = b.info ? b.info + 3 * k : nullptr;
+  double *tph = dbg ? dbg + 2 * (long)gridDim.x + 8 * (long)k : nullptr;
+  if (tph && tid == 0)
+    for (int e = 0; e < 8; ++e) tph[e] = 0.0;
+  if (n <= 256)
+    lanczos_plain<1>(Gk, n, ld, Vk, v, L, max_restart, tol, info3, &steps, tph);
+  else
+    lanczos_plain<2>(Gk, n, ld, Vk, v, L, max_restart, tol, info3, &steps, tph);
   if (dbg && tid == 0)
     dbg[2 * k] = (double)steps, dbg[2 * k + 1] = (double)(wall_clock64() - t_dbg) * 0.01;
 }
 
+// ------------------------------------------------------------------------------------
+// Restarted Lanczos with full (twice-applied classical Gram-Schmidt) re-orthogonalisation, for
+// launches whose largest matrix has more than LP_NMAX columns.  One block of 1024 threads per
+// matrix; the Krylov basis (LANCZOS_M + 2 rows of length ld) lives in global scratch (L2
+// resident).  The small tridiagonal problem is solved by wave 0 (tridiag_top_lean).
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum(double v, double *red) {
+  v = wave_sum_d(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) t += red[w];
+  return t;
+}
+
+__global__ __launch_bounds__(1024) void lanczos_kernel(EigBatch b, int max_restart, double tol) {
+  __shared__ double alpha[LANCZOS_M], beta[LANCZOS_M], h[LANCZOS_M + 1];
+  __shared__ TriWork ws;
+  __shared__ double red[16];
+  __shared__ double upd[4][256];
+  __shared__ double s_theta;
+  extern __shared__ __align__(16) double lz_dyn[];  // SmallWork, or the squaring buffers
+  double *svec = ws.x;
+  const int k = blockIdx.x;
+  if (eig_power_front<16>(b, EigSlabs(), k, lz_dyn)) return;
+  const int n = (int)b.n[k], ld = (int)b.ld[k];
+  double *const info = b.info, *const dbg = b.dbg;
+  const unsigned long long t_dbg = dbg ? wall_clock64() : 0ull;  // 100 MHz
+  int steps_dbg = 0;
+  const double *Gk = b.G + b.g_off[k];
+  double *Qk = b.Q + b.q_off[k];  // (LANCZOS_M + 2) rows of length ld; last row = Ritz vector
+  double *y = Qk + (long)(LANCZOS_M + 1) * ld;
+  double *v = b.v + b.v_off[k];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int mfull = min(LANCZOS_M, n);
+
+  // start vector: G * ones (a few power-like steps come for free in the Krylov space)
+  for (int r = wave; r < n; r += 16) {
+    double acc = 0.0;
+    for (int c = lane; c < n; c += 64) acc += Gk[(long)r * ld + c];
+    acc = wave_sum_d(acc);
+    if (lane == 0) y[r] = acc;
+  }
+  __syncthreads();
+  double theta = 0.0, resid = 0.0;
+  int restarts = 0;
+  for (; restarts < max_restart; ++restarts) {
+    // q_0 = y / |y|
+    double p = 0.0;
+    for (int e = tid; e < n; e += 1024) p = fma(y[e], y[e], p);
+    const double nrm = sqrt(block_sum(p, red));
+    const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+    for (int e = tid; e < n; e += 1024) Qk[e] = (nrm > 0.0) ? y[e] * inv : (e == 0 ? 1.0 : 0.0);
+    __syncthreads();
+    int m = 0;
+    double beta_last = 0.0;
+    // a dominant nuisance converges in a few steps: the Ritz pair is tested at LANCZOS_M/2
+    // and 3/4 LANCZOS_M, and the recurrence goes on from there (no restart) when it fails
+    const int mmax = mfull;
+    bool solved = false;
+    for (int j = 0; j < mmax; ++j) {
+      const double *qj = Qk + (long)j * ld;
+      double *w = Qk + (long)(j + 1) * ld;
+      // w = G q_j.  G is symmetric: thread r accumulates sum_c G[c][r] q_j[c], so that lanes
+      // read consecutive addresses and no cross-lane reduction is needed; the columns are
+      // split over 4 groups of 256 threads and combined through LDS.
+      {
+        const int part = tid >> 8, r0 = tid & 255;
+        for (int rb = 0; rb < n; rb += 256) {
+          const int r = rb + r0;
+          double acc = 0.0;
+          if (r < n) {
+            // G comes from L2 (~0.7 us per round trip): 16 loads per lane in flight
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            int c = part;
+            for (; c + 60 < n; c += 64) {
+              double g[16];
+#pragma unroll
+              for (int q = 0; q < 16; ++q) g[q] = Gk[(long)(c + 4 * q) * ld + r];
+#pragma unroll
+              for (int q = 0; q < 16; q += 4) {
+                a0 = fma(g[q], qj[c + 4 * q], a0);
+                a1 = fma(g[q + 1], qj[c + 4 * q + 4], a1);
+                a2 = fma(g[q + 2], qj[c + 4 * q + 8], a2);
+                a3 = fma(g[q + 3], qj[c + 4 * q + 12], a3);
+              }
+            }
+            for (; c < n; c += 4) a0 = fma(Gk[(long)c * ld + r], qj[c], a0);
+            acc = (a0 + a1) + (a2 + a3);
+          }
+          upd[part][r0] = acc;
+          __syncthreads();
+          if (part == 0 && r < n) w[r] = (upd[0][r0] + upd[1][r0]) + (upd[2][r0] + upd[3][r0]);
+          __syncthreads();
+        }
+      }
+      // classical Gram-Schmidt against q_0..q_j, twice; alpha_j = first-pass h_j (+ fix)
+      double aj = 0.0;
+      for (int pass = 0; pass < 2; ++pass) {
+        for (int i = wave; i <= j; i += 16) {
+          const double *qi = Qk + (long)i * ld;
+          double acc = 0.0;
+#pragma unroll 4
+          for (int c = lane; c < n; c += 64) acc = fma(qi[c], w[c], acc);
+          acc = wave_sum_d(acc);
+          if (lane == 0) h[i] = acc;
+        }
+        __syncthreads();
+        aj += h[j];
+        // w -= Q h with the j+1 rows split over 4 thread groups (independent loads in
+        // flight instead of one dependent chain per element), combined through LDS
+        {
+          const int part = tid >> 8, e0 = tid & 255;
+          for (int eb = 0; eb < n; eb += 256) {
+            const int e = eb + e0;
+            double acc = 0.0;
+            if (e < n) {
+#pragma unroll 4
+              for (int i = part; i <= j; i += 4) acc = fma(h[i], Qk[(long)i * ld + e], acc);
+            }
+            upd[part][e0] = acc;
+            __syncthreads();
+            if (part == 0 && e < n)
+              w[e] -= (upd[0][e0] + upd[1][e0]) + (upd[2][e0] + upd[3][e0]);
+            __syncthreads();
+          }
+        }
+      }
+      double pw = 0.0;
+      for (int e = tid; e < n; e += 1024) pw = fma(w[e], w[e], pw);
+      const double bj = sqrt(block_sum(pw, red));
+      if (tid == 0) alpha[j] = aj, beta[j] = bj;
+      m = j + 1;
+      beta_last = bj;
+      // invariant subspace reached (also the exact case m == n)
+      if (bj <= 1e-300 || bj <= 1e-15 * fabs(aj)) break;
+      if (j + 1 < mmax) {
+        const double ib = 1.0 / bj;
+        for (int e = tid; e < n; e += 1024) w[e] *= ib;
+      }
+      __syncthreads();
+      if (j + 1 < mmax && (j + 1 == LANCZOS_M / 2 || j + 1 == 3 * LANCZOS_M / 4)) {
+        if (wave == 0) {
+          const double th = tridiag_top_lean(alpha, beta, m, lane, ws);
+          if (lane == 0) s_theta = th;
+        }
+        __syncthreads();
+        solved = fabs(bj * svec[m - 1]) <= tol * fabs(s_theta);  // block-uniform
+        if (solved) break;
+      }
+    }
+    __syncthreads();
+    // ---- largest eigenpair of T_m (wave 0)
+    if (!solved) {
+      if (wave == 0) {
+        const double th = tridiag_top_lean(alpha, beta, m, lane, ws);
+        if (lane == 0) s_theta = th;
+      }
+      __syncthreads();
+    }
+    theta = s_theta;
+    // y = Q s
+    for (int e = tid; e < n; e += 1024) {
+      double acc = 0.0;
+#pragma unroll 8
+      for (int i = 0; i < m; ++i) acc = fma(svec[i], Qk[(long)i * ld + e], acc);
+      y[e] = acc;
+    }
+    resid = fabs(beta_last * svec[m - 1]);
+    steps_dbg += m;
+    __syncthreads();
+    if (m >= n || resid <= tol * fabs(theta)) break;
+  }
+  // final normalisation of the eigenvector
+  double p = 0.0;
+  for (int e = tid; e < n; e += 1024) p = fma(y[e], y[e], p);
+  const double nrm = sqrt(block_sum(p, red));
+  const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+  for (int e = tid; e < n; e += 1024) v[e] = y[e] * inv;
+  for (int e = n + tid; e < ld; e += 1024) v[e] = 0.0;
+  if (tid == 0 && info) {
+    info[3 * k] = theta;
+    info[3 * k + 1] = resid;
+    info[3 * k + 2] = (double)restarts;
+  }
+  if (tid == 0 && dbg) dbg[2 * k] = (double)steps_dbg, dbg[2 * k + 1] = (double)(wall_clock64() - t_dbg) * 0.01;
+}
+
+// Which kernel takes a launch, and the dynamic LDS it runs with.
+enum EigKernel { EIG_POWER, EIG_PLAIN, EIG_RESTARTED };
+struct EigDispatch {
+  EigKernel kernel;
+  size_t lds;
+};
+constexpr size_t EIG_LDS_MAX[3] = {PW_BYTES, std::max(PW_BYTES, LP_BYTES), PW_BYTES};
+static_assert(sizeof(SmallWork) <= PW_BYTES, "SmallWork overlays the squaring buffers");
+
+EigDispatch eig_dispatch(long ldmax, bool slabs) {
+  if (slabs || ldmax <= PW_N) return {EIG_POWER, ldmax > LANCZOS_M ? PW_BYTES : sizeof(SmallWork)};
+  if (ldmax <= LP_NMAX) return {EIG_PLAIN, EIG_LDS_MAX[EIG_PLAIN]};
+  return {EIG_RESTARTED, EIG_LDS_MAX[EIG_RESTARTED]};
+}
+
 }  // namespace
 
-// launches lanczos_kernel with the basis in LDS when the largest matrix allows it
-int origin_pca_eig_launch(origin_ctx *ctx, int nmat, long ldmax, const double *d_G,
-                          const long *d_g_off, const long *d_ld, const long *d_n, double *d_q,
-                          const long *d_q_off, double *d_v, const long *d_v_off, double *d_info,
-                          const double *d_slab, long slab_stride, int ksplit, double *d_dbg) {
+int origin_pca_eig_launch(origin_ctx *ctx, const EigBatch &batch, long ldmax, EigSlabs slabs) {
+  // dynamic + static LDS must stay within the 160 KB of a CU: every kernel asks for exactly what
+  // its largest launch uses
   static OriginPerDeviceOnce attr_once;
-  // dynamic + static LDS must stay within the 160 KB of a CU: ask for exactly what is used
-  const int dyn_max = (int)std::max(PW_BYTES, (size_t)(LANCZOS_M + 2) * LANCZOS_QLDS_LD * sizeof(double));
-  ORIGIN_ONCE_PER_DEVICE(ctx, attr_once,
-                         ORIGIN_HIP(hipFuncSetAttribute((const void *)lanczos_kernel<true>,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        dyn_max));
-                         ORIGIN_HIP(hipFuncSetAttribute((const void *)lanczos_kernel<false>,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        dyn_max)));
-  // Above PW_N columns: plain Lanczos with the matrix resident on the CU (lanczos_plain_kernel).
-  // A launch whose largest matrix exceeds LP_NMAX columns goes to lanczos_kernel as a whole.
-  if (!d_slab && ldmax > PW_N && ldmax <= LP_NMAX) {
-    static OriginPerDeviceOnce attr_plain;
-    const size_t lds = std::max(std::max(PW_BYTES, sizeof(SmallWork)), LP_BYTES);
-    ORIGIN_ONCE_PER_DEVICE(ctx, attr_plain,
-                           ORIGIN_HIP(hipFuncSetAttribute((const void *)lanczos_plain_kernel,
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                          (int)lds)));
-    hipLaunchKernelGGL(lanczos_plain_kernel, dim3(nmat), dim3(LP_NT), lds, ctx->stream, d_G, d_g_off,
-                       d_ld, d_n, d_q, d_q_off, d_v, d_v_off, 8, 1e-14, d_info, d_dbg);
-    ORIGIN_LAUNCH_CHECK();
-    return ORIGIN_OK;
-  }
-  // matrices of up to PW_N columns are solved by repeated squaring in LDS (PW_BYTES of it)
-  const bool mid = ldmax > LANCZOS_M;
-  const bool qlds = ldmax <= LANCZOS_QLDS_LD;
-  if (qlds) {
-    size_t lds = std::max(sizeof(SmallWork),
-                          (size_t)(LANCZOS_M + 2) * (size_t)ldmax * sizeof(double));
-    if (mid) lds = std::max(lds, PW_BYTES);
-    hipLaunchKernelGGL(lanczos_kernel<true>, dim3(nmat), dim3(1024), lds, ctx->stream, d_G, d_g_off,
-                       d_ld, d_n, d_q, d_q_off, d_v, d_v_off, 60, 1e-14, d_info, d_slab, slab_stride,
-                       ksplit, mid ? PW_N : 0, d_dbg);
-  } else {
-    hipLaunchKernelGGL(lanczos_kernel<false>, dim3(nmat), dim3(1024),
-                       std::max(sizeof(SmallWork), PW_BYTES), ctx->stream, d_G, d_g_off, d_ld, d_n,
-                       d_q, d_q_off, d_v, d_v_off, 60, 1e-14, d_info, d_slab, slab_stride, ksplit,
-                       PW_N, d_dbg);
-  }
+  const void *const kernels[3] = {(const void *)eig_power_kernel, (const void *)lanczos_plain_kernel,
+                                  (const void *)lanczos_kernel};
+  ORIGIN_ONCE_PER_DEVICE(ctx, attr_once, {
+    for (int i = 0; i < 3; ++i)
+      ORIGIN_HIP(hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)EIG_LDS_MAX[i]));
+  });
+  const EigDispatch d = eig_dispatch(ldmax, slabs.ptr != nullptr);
+  const dim3 grid(batch.nmat);
+  if (d.kernel == EIG_POWER)
+    hipLaunchKernelGGL(eig_power_kernel, grid, dim3(1024), d.lds, ctx->stream, batch, slabs);
+  else if (d.kernel == EIG_PLAIN)
+    hipLaunchKernelGGL(lanczos_plain_kernel, grid, dim3(LP_NT), d.lds, ctx->stream, batch, 8, 1e-14);
+  else
+    hipLaunchKernelGGL(lanczos_kernel, grid, dim3(1024), d.lds, ctx->stream, batch, 60, 1e-14);
   ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }
@@ -1450,8 +1296,9 @@ int origin_pca_eig(origin_ctx *ctx, const double *d_G, const long *d_g_off, cons
   long ldmax = 0;
   for (long x : h_ld) ldmax = std::max(ldmax, x);
   ProfScope ps(ctx, K_PCA_EIG, 2);
-  return origin_pca_eig_launch(ctx, nmat, ldmax, d_G, d_g_off, d_ld, d_n, (double *)scr, d_q_off,
-                               d_v, d_v_off, d_info);
+  return origin_pca_eig_launch(ctx, EigBatch{nmat, d_G, d_g_off, d_ld, d_n, (double *)scr, d_q_off,
+                                             d_v, d_v_off, d_info, nullptr},
+                               ldmax);
 }
 
 int origin_pca_eig_qrows(void) { return EIG_QROWS; }

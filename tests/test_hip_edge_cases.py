@@ -282,7 +282,7 @@ def test_pca_more_iterations_than_vector_slots(hip):
 
 def test_pca_area_larger_than_the_register_resident_selection(hip):
     """An area of more than 1024 x 12 spaxels takes the general selection kernel (O2 values
-    streamed instead of held in registers / LDS), the re-gathered background mean and the
+    streamed from memory instead of held in registers), the re-gathered background mean and the
     per-area deflation kernels."""
     rng = np.random.default_rng(47)
     Nz, S = 64, 13000
@@ -298,6 +298,40 @@ def test_pca_area_larger_than_the_register_resident_selection(hip):
     assert ref[1].max() >= 5
     assert got[2] == ref[2] and np.array_equal(got[1], ref[1])
     assert np.max(np.abs(got[0] - ref[0])) <= 1e-4
+
+
+@pytest.mark.parametrize("itermax,nstop,depth", [(100, 0, 12), (3, 1, 4)])
+def test_pca_general_selection_stop_rules(ctx, itermax, nstop, depth):
+    """The stop rules of the general selection kernel (they are the code the register-resident
+    kernel runs too): an area of more than 1024 x 12 spaxels next to one that stops at its first
+    selection (no spaxel above its threshold: n == 0) and a few spaxels outside every area; the
+    large area runs to its end (itermax = 100, twelve iterations) or is stopped by itermax = 3
+    (mapO2 counts the fourth selection, nstop = 1)."""
+    from origin_amd import pipeline
+    rng = np.random.default_rng(53)
+    Nz, Ny, Nx = 64, 104, 128
+    cube = rng.standard_normal((Nz, Ny, Nx)).astype(np.float32)
+    areamap = np.ones((Ny, Nx), int)
+    areamap[-2:, :] = 2
+    areamap[0, :8] = 0
+    idx1 = np.nonzero(areamap.reshape(-1) == 1)[0]
+    assert len(idx1) > 1024 * 12                    # the launch takes the general kernel
+    flat = cube.reshape(Nz, -1)
+    for j in range(12):
+        flat[:, idx1[1000 * j + 7]] += np.float32(5.0 + 0.3 * j) * rng.standard_normal(Nz).astype(np.float32)
+    X = cube.astype(float)
+    tests = [cpu_ref.O2test(X[:, areamap == a + 1]) for a in range(2)]
+    thr = [float(np.sort(tests[0])[-13]), float(tests[1].max() + 1)]
+    ref = cpu_ref.Compute_GreedyPCA_area(2, X, areamap, 50, thr, itermax, tests, svd="dense")
+    assert ref[2] == nstop and ref[1].max() == depth
+    F, mapO2, got_nstop, _ = pipeline.greedy_pca(ctx, ctx.to_device(cube), areamap, 2, thr, tests,
+                                                 50, itermax)
+    got = F.to_host()
+    assert np.array_equal(mapO2, ref[1])
+    assert got_nstop == ref[2]
+    assert np.max(np.abs(got - ref[0])) <= 1e-4
+    for a in (0, 2):
+        assert np.array_equal(got[:, areamap == a], cube[:, areamap == a])
 
 
 @pytest.mark.parametrize("deep", [False, True])

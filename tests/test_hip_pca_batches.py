@@ -232,7 +232,7 @@ def check_pair(spec, v, info):
     assert np.all(v[n:] == 0), spec
     got = v[:n]
     assert abs(np.linalg.norm(got) - 1) < 1e-12, spec
-    if kind == "zero":   # tridiag_top's convention for T == 0: eigenvalue 0, a unit vector
+    if kind == "zero":   # tridiag_top_lean's convention for T == 0: eigenvalue 0, a unit vector
         assert theta == 0.0, spec
         return
     assert abs(theta - w[-1]) <= 1e-12 * w[-1], (spec, theta, w[-1])
@@ -279,15 +279,15 @@ ROUND2_BATCH = [(513, "gap"), (1, "flat"), (20, "lowrank"), (49, "close"), (96, 
 
 
 def test_eig_batch_small_launch(ctx):
-    """ldmax <= LANCZOS_M: lanczos_kernel<true> without the mid solver (power_nmax = 0, dynamic LDS
-    = SmallWork only); every block in eig_small_power<16> with one, two and three tile rows."""
+    """ldmax <= LANCZOS_M: eig_power_kernel with dynamic LDS = SmallWork only; every block in
+    eig_small_power<16> with one, two and three tile rows."""
     assert max(ld_of(n) for n, _ in SMALL_BATCH) <= LANCZOS_M
     check_batch(ctx, SMALL_BATCH)
 
 
 def test_eig_batch_mid_launch(ctx):
-    """LANCZOS_M < ldmax <= PW_N: lanczos_kernel<true> with `mid` (dynamic LDS = PW_BYTES); blocks
-    with n <= LANCZOS_M overlay SmallWork on it (eig_small_power<16>), the others run
+    """LANCZOS_M < ldmax <= PW_N: eig_power_kernel with dynamic LDS = PW_BYTES; blocks with
+    n <= LANCZOS_M overlay SmallWork on it (eig_small_power<16>), the others run
     eig_mid_power<16>."""
     assert LANCZOS_M < max(ld_of(n) for n, _ in MID_BATCH) <= PW_N
     check_batch(ctx, MID_BATCH)
@@ -304,10 +304,9 @@ def test_eig_batch_plain_launch(ctx, reverse):
 
 
 def test_eig_batch_round2_launch(ctx):
-    """ldmax > LP_NMAX: lanczos_kernel<false> (basis in the global scratch at q_off, dynamic LDS
-    = max(SmallWork, PW_BYTES)): the 513-column matrix and a 130-column one in the restarted
-    Lanczos with the basis at their own q_off, the small ones in eig_small_power<16> /
-    eig_mid_power<16> next to them."""
+    """ldmax > LP_NMAX: lanczos_kernel (basis in the global scratch at q_off, dynamic LDS =
+    PW_BYTES): the 513-column matrix and a 130-column one in the restarted Lanczos with the basis
+    at their own q_off, the small ones in eig_small_power<16> / eig_mid_power<16> next to them."""
     assert max(ld_of(n) for n, _ in ROUND2_BATCH) > LP_NMAX
     check_batch(ctx, ROUND2_BATCH)
 
@@ -328,7 +327,7 @@ def test_eig_batch_with_all_zero_matrices(ctx, launch):
     """An all-zero matrix in every per-matrix branch next to ordinary ones: eig_small_power and
     eig_mid_power (trace 0: first unit vector), lanczos_plain (breakdown at the first step,
     tridiag_top_lean's T == 0) in lanczos_plain_kernel; the two power solvers and the restarted
-    Lanczos (tridiag_top's T == 0) in lanczos_kernel<false>.  Every loop of the three solvers is
+    Lanczos (the same T == 0 branch) in lanczos_kernel.  Every loop of the three solvers is
     bounded whatever the data (fixed squaring count of 64, restart caps of 60 / 8, mmax steps), so
     the case can only fail, not hang.  Zero matrices come back finite with theta == 0 and a unit
     vector; their neighbours meet the usual tolerances."""
@@ -530,10 +529,10 @@ def test_pca_areas_of_mixed_batch_sizes(hip, cases):
 @pytest.mark.parametrize("twin", [False, True])
 def test_pca_all_small_switch(hip, cases, twin):
     """The all_small path of enqueue_chain (w.ldmax <= LANCZOS_M: gram_reduce_kernel skipped,
-    lanczos_kernel<true> sums the K-split slabs itself) at Nz = 200, ksplit = 3: four areas that
+    eig_power_kernel sums the K-split slabs itself) at Nz = 200, ksplit = 3: four areas that
     never have more than 48 nuisance spaxels, so every iteration takes it; and (twin) one area
     that starts at 60 and falls to 48 or below after a few iterations, so the run starts on the
-    reduced-Gram path (lanczos_kernel<true> with `mid`) and changes to the slab path while three
+    reduced-Gram path (eig_power_kernel on G) and changes to the slab path while three
     areas still iterate."""
     c = cases("twin" if twin else "small")
     ntiles = sum(len(np.triu_indices((ld_of(n) + 31) // 32)[0]) for n in c.first_counts())
