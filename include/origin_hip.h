@@ -155,6 +155,35 @@ int origin_fits_write_data(origin_ctx *ctx, const void *d_src, int src_type, lon
                            int fd);
 int origin_fits_read_data(origin_ctx *ctx, int fd, int bitpix, long n, int dst_type, void *d_dst);
 
+/* ---- step 0: a MUSE cube file becomes cube_raw / var / mask and the white image ----------
+ * ORIGIN.__init__ reads the cube through mpdaf (origin.py:210-219), whose Cube masks the voxels
+ * where DATA or STAT is not finite, and derives from it (origin.py:262-274, :240)
+ *     cube_raw = cube.data.filled(0);  var = cube.var.filled(inf);  mask = cube._mask
+ *     ima_white = cube.mean(axis=0)
+ * origin_cube_ingest_planes is that pass for `nplanes` consecutive planes whose big-endian file
+ * bytes (BITPIX -32 or -64 each; 8-byte aligned) already sit on the device.  Per voxel, with d / s
+ * the DATA / STAT value as float32 (-64: rounded, so a value beyond the float32 range is inf):
+ *     m = !isfinite(d) || !isfinite(s);  raw = m ? 0 : d;  var = m ? inf : s;  mask = m
+ * finite values bit for bit.  d_raw / d_var / d_mask point at the first of the planes.
+ * d_white_sum[S] (float64) / d_white_cnt[S] (int32) are running: sum += (double) raw plane after
+ * plane in increasing z, cnt += !m -- the plane-by-plane float64 sum of NumPy, however the planes
+ * are split into calls.  The caller zeroes both before the first plane (origin_memset).
+ * 16-byte accesses where S % 4 == 0 and every pointer is 16-byte aligned (d_mask: 4).
+ * Asynchronous on the context's stream. */
+int origin_cube_ingest_planes(origin_ctx *ctx, const void *d_data_be, int bitpix_data,
+                              const void *d_stat_be, int bitpix_stat, int nplanes, long S,
+                              float *d_raw, float *d_var, uint8_t *d_mask, double *d_white_sum,
+                              int *d_white_cnt);
+/* The same from an open file (replaces the float64 host read of Cube(filename), origin.py:213):
+ * pread at the byte offsets of the two data units into two pinned buffers, chunk by chunk a whole
+ * number of planes, H2D copy then kernel, file reads overlapping both as in origin_fits_read_data.
+ * planes_per_chunk == 0: as many planes as fit 64 MiB of file bytes, at least 1.  Zeroes the sums
+ * itself.  A short read gives ORIGIN_E_STATE after the stream has drained.  Returns when the
+ * arrays are complete. */
+int origin_cube_read(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
+                     int bitpix_stat, int Nz, long S, int planes_per_chunk, float *d_raw,
+                     float *d_var, uint8_t *d_mask, double *d_white_sum, int *d_white_cnt);
+
 /* ---- inter-GPU exchange (one process per GPU; RCCL over xGMI on the context's stream) ----
  * The reference has no multi-GPU path (its only parallelism is the joblib pool of
  * lib_origin.py:1150-1160); these serve the spatial tiling of origin_amd/multigpu.py.

@@ -50,6 +50,8 @@ SIGNATURES = {
     "origin_fits_decode": [vp, vp, i32, i64, i32, vp],
     "origin_fits_write_data": [vp, vp, i32, i64, i32, i32],
     "origin_fits_read_data": [vp, i32, i32, i64, i32, vp],
+    "origin_cube_ingest_planes": [vp, vp, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp],
+    "origin_cube_read": [vp, i32, i64, i32, i64, i32, i32, i64, i32, vp, vp, vp, vp, vp],
     "origin_comm_unique_id": [vp],
     "origin_comm_create": [vp, vp, i32, i32, PP(vp)],
     "origin_comm_destroy": [vp],

@@ -207,6 +207,21 @@ int carve_block(origin_ctx *ctx, DevMem &mem, Layout &&layout) {
   return ORIGIN_OK;
 }
 
+// Streamed file I/O (fits.hip, ingest.hip): a data unit moves in chunks of at most this many
+// bytes through two pinned host buffers, each with the event that says its copy has drained.
+constexpr long IO_CHUNK_BYTES = 64l << 20;
+
+struct IoStage {
+  void *h[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~IoStage() {
+    for (int i = 0; i < 2; ++i) {
+      if (h[i]) (void)hipHostFree(h[i]);
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+    }
+  }
+};
+
 template <class T>
 int put(origin_ctx *ctx, T *d, const std::vector<T> &h) {
   return origin_h2d(ctx, d, h.data(), h.size() * sizeof(T));

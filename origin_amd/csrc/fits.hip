@@ -209,19 +209,6 @@ int origin_fits_decode(origin_ctx *ctx, const void *d_src, int bitpix, long n, i
 // system, the PCIe copy and the kernel overlap.  Sequential I/O at the descriptor's offset.
 namespace {
 
-constexpr long IO_CHUNK_BYTES = 64l << 20;
-
-struct IoStage {
-  void *h[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~IoStage() {
-    for (int i = 0; i < 2; ++i) {
-      if (h[i]) (void)hipHostFree(h[i]);
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-  }
-};
-
 int write_all(int fd, const char *p, size_t bytes) {
   while (bytes) {
     const ssize_t w = ::write(fd, p, bytes);

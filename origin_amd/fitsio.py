@@ -18,8 +18,10 @@ I/O overlapping), so a cube in HBM reaches the file without a host-side conversi
 library these functions raise.
 """
 import ctypes as C
+import logging
 import os
-from collections import OrderedDict
+import re
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
@@ -332,6 +334,176 @@ class FitsCube:
         if key not in self._dev:
             self._dev[key] = read_image(self.path, self.ext, key, ctx)[0]
         return self._dev[key]
+
+
+# ------------------------------------------------------------------------------- step 0
+# The session's way in (reference origin.py:210-244): a MUSE cube file -- primary HDU, then IMAGE
+# extensions DATA and STAT (mpdaf's Cube layout) -- becomes cube_raw / var / mask in HBM and the
+# white image, through origin_cube_read (csrc/ingest.hip).  Headers are host work; the voxels
+# never exist on the host.
+_SPATIAL_CARD = re.compile(r"^(C(TYPE|UNIT|RPIX|RVAL|DELT|ROTA)[12]|(CD|PC)[12]_[12]|RADESYS|EQUINOX|"
+                           r"LONPOLE|LATPOLE)$")
+_SPECTRAL_CARD = re.compile(r"^(C(TYPE|UNIT|RPIX|RVAL|DELT)3|(CD|PC)(3_[123]|[12]_3))$")
+
+CubeFile = namedtuple("CubeFile", "path shape off_data bitpix_data off_stat bitpix_stat "
+                                  "wcs_header wave_header primary_header")
+
+
+def open_cube(path):
+    """The layout of a cube file, checked before any device call: a ``CubeFile`` with the shape
+    ``(Nz, Ny, Nx)``, the byte offsets and BITPIX of the DATA and STAT data units, the spatial
+    (``wcs_header``) and spectral (``wave_header``) world-coordinate cards of the DATA header as
+    plain mappings -- what ``Step.dump`` writes back -- and the primary header.
+
+    DATA and STAT are found by EXTNAME, in either order; both must be 3-D IMAGE extensions of the
+    same shape, BITPIX -32 or -64, without BSCALE / BZERO, and wholly in the file: anything else
+    is a ``ValueError`` naming the file and the reason.  A DQ extension is *ignored*, with a
+    warning: mpdaf would mask the voxels it flags, here the mask is the non-finite voxels of DATA
+    and STAT alone (what a MUSE pipeline cube carries: its DQ is folded into NaNs)."""
+    try:
+        hdus = scan(path)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
+    found = {}
+    for h in hdus[1:]:
+        name = str(h[0].get("EXTNAME", "")).strip().upper()
+        if h[0].get("XTENSION") == "IMAGE" and name in ("DATA", "STAT", "DQ") and name not in found:
+            found[name] = h
+    for name in ("DATA", "STAT"):
+        if name not in found:
+            raise ValueError(f"{path}: no {name} image extension")
+    if "DQ" in found:
+        logging.getLogger(__name__).warning(
+            "%s: the DQ extension is ignored (only non-finite DATA / STAT voxels are masked)", path)
+    size = os.path.getsize(path)
+    shapes = {}
+    for name in ("DATA", "STAT"):
+        hdr, off, nb = found[name]
+        if hdr.get("NAXIS") != 3:
+            raise ValueError(f"{path}: {name} has NAXIS = {hdr.get('NAXIS')}, a cube has 3")
+        if hdr["BITPIX"] not in (-32, -64):
+            raise ValueError(f"{path}: {name} has BITPIX = {hdr['BITPIX']}, only -32 and -64 are read")
+        if hdr.get("BSCALE", 1) != 1 or hdr.get("BZERO", 0) != 0:
+            raise ValueError(f"{path}: {name} is scaled (BSCALE / BZERO), which is not supported")
+        if size < off + nb:
+            raise ValueError(f"{path}: the {name} data unit is truncated "
+                             f"({off + nb - size} bytes missing)")
+        shapes[name] = tuple(int(hdr[f"NAXIS{i}"]) for i in (3, 2, 1))
+    if shapes["DATA"] != shapes["STAT"]:
+        raise ValueError(f"{path}: DATA is {shapes['DATA']} but STAT is {shapes['STAT']}")
+    if 0 in shapes["DATA"]:
+        raise ValueError(f"{path}: empty cube {shapes['DATA']}")
+    hdr = found["DATA"][0]
+    wcs = OrderedDict((k, v) for k, v in hdr.items() if _SPATIAL_CARD.match(k))
+    wave = OrderedDict((k, v) for k, v in hdr.items() if _SPECTRAL_CARD.match(k))
+    return CubeFile(path, shapes["DATA"], found["DATA"][1], hdr["BITPIX"], found["STAT"][1],
+                    found["STAT"][0]["BITPIX"], wcs, wave, hdus[0][0])
+
+
+def read_cube(path, ctx=None, planes_per_chunk=0):
+    """``(raw, var, mask, ima_white, wcs_header, wave_header)`` of a cube file: the float32 /
+    float32 / uint8 device arrays as ``ORIGIN.init`` leaves cube_raw, var and mask (0 / inf / 1 at
+    the voxels where DATA or STAT is not finite as float32, origin.py:262-274), the white image
+    on the host (float64 mean over the unmasked voxels of each spaxel, NaN where there is none;
+    origin.py:240) and the two card mappings of ``open_cube``.  The file bytes go to HBM as they
+    are, in chunks of ``planes_per_chunk`` planes (0: 64 MiB), and one kernel does the rest."""
+    info = open_cube(path)
+    ctx = ctx or default_context(0)
+    Nz, Ny, Nx = info.shape
+    S = Ny * Nx
+    raw, var = DeviceArray(ctx, info.shape, np.float32), DeviceArray(ctx, info.shape, np.float32)
+    mask = DeviceArray(ctx, info.shape, np.uint8)
+    wsum, wcnt = DeviceArray(ctx, (Ny, Nx), np.float64), DeviceArray(ctx, (Ny, Nx), np.int32)
+    with open(path, "rb", buffering=0) as f:
+        _capi.call("origin_cube_read", ctx.handle, f.fileno(), info.off_data, info.bitpix_data,
+                   info.off_stat, info.bitpix_stat, Nz, S, int(planes_per_chunk), raw.p, var.p,
+                   mask.p, wsum.p, wcnt.p)
+    ima_white = white_image(wsum.to_host(), wcnt.to_host())
+    wsum.free()
+    wcnt.free()
+    return raw, var, mask, ima_white, info.wcs_header, info.wave_header
+
+
+def white_image(wsum, wcnt):
+    """sum / count, NaN where the count is 0 (the masked mean of origin.py:240)."""
+    out = np.full(wsum.shape, np.nan)
+    np.divide(wsum, wcnt, out=out, where=wcnt > 0)
+    return out
+
+
+def read_profiles(path):
+    """``(profiles, FWHM_profiles)`` of a dictionary of spectral profiles: the 1-D array of every
+    HDU after the primary as float64, and its ``FWHM`` card (reference origin.py:515-533).  Host
+    work: a few kilobytes."""
+    profiles, fwhm = [], []
+    with open(path, "rb") as f:
+        for hdr, off, nb in scan(path)[1:]:
+            if hdr.get("BITPIX") not in _DTYPE_OF or not nb:
+                raise ValueError(f"{path}: extension {hdr.get('EXTNAME')!r} holds no profile")
+            if "FWHM" not in hdr:
+                raise ValueError(f"{path}: extension {hdr.get('EXTNAME')!r} has no FWHM card")
+            f.seek(off)
+            p = np.frombuffer(f.read(nb), dtype=_DTYPE_OF[hdr["BITPIX"]].newbyteorder(">"))
+            profiles.append(p.astype(np.float64) * hdr.get("BSCALE", 1) + hdr.get("BZERO", 0))
+            fwhm.append(hdr["FWHM"])
+    if not profiles:
+        raise ValueError(f"{path}: no profile")
+    if len({p.shape[0] for p in profiles}) != 1:
+        raise ValueError("The profiles must have the same size")
+    return profiles, fwhm
+
+
+def read_host_image(path, ext=None):
+    """Host array of an image HDU with the file's own type, read with NumPy alone (the PSF cubes
+    and weight maps of a session: ``fits.getdata``, origin.py:619, :641-643).  ``ext=None``: the
+    first HDU that holds data."""
+    hdus = scan(path)
+    if ext is None:
+        hdu = next((h for h in hdus if h[2] and h[0].get("XTENSION", "IMAGE") == "IMAGE"), None)
+        if hdu is None:
+            raise ValueError(f"{path}: no image data")
+    else:
+        hdu = find_hdu(path, ext)
+    hdr, off, nb = hdu
+    shape = tuple(hdr[f"NAXIS{i}"] for i in range(hdr["NAXIS"], 0, -1))
+    with open(path, "rb") as f:
+        f.seek(off)
+        buf = f.read(nb)
+    if len(buf) < nb:
+        raise ValueError(f"{path}: truncated data unit")
+    dt = _DTYPE_OF[hdr["BITPIX"]]
+    arr = np.frombuffer(buf, dtype=dt.newbyteorder(">")).astype(dt).reshape(shape)
+    if hdr.get("BSCALE", 1) != 1 or hdr.get("BZERO", 0) != 0:
+        arr = arr * hdr.get("BSCALE", 1) + hdr.get("BZERO", 0)
+    return arr
+
+
+def write_cube(path, data, stat, header=None, bitpix=-32, primary_header=None, stat_first=False,
+               dq=None):
+    """Write host arrays as a cube file -- ``<primary, no data> + DATA + STAT`` image extensions,
+    mpdaf's layout -- with NumPy alone: for the synthetic fields, the tests and the timing tool.
+    ``bitpix``: -32 / -64, or a pair (DATA, STAT).  ``header``: further cards of both extensions
+    (the world coordinates); ``primary_header``: of the primary HDU.  ``stat_first`` swaps the two
+    extensions; ``dq``: an integer cube written as a third extension DQ (BITPIX 32)."""
+    bd, bs = bitpix if isinstance(bitpix, (tuple, list)) else (bitpix, bitpix)
+    units = [("DATA", np.asarray(data), bd), ("STAT", np.asarray(stat), bs)]
+    if stat_first:
+        units.reverse()
+    if dq is not None:
+        units.append(("DQ", np.asarray(dq), 32))
+    tmp = path + ".part"
+    with open(tmp, "wb") as f:
+        f.write(header_bytes(_image_cards((), 8, True, extra=primary_header)))
+        for name, arr, bp in units:
+            if bp not in (-32, -64, 32):
+                raise ValueError(f"BITPIX {bp} is not written")
+            f.write(header_bytes(_image_cards(arr.shape, bp, False, name,
+                                              header if name != "DQ" else None)))
+            raw = np.ascontiguousarray(arr, dtype=_DTYPE_OF[bp].newbyteorder(">"))
+            f.write(raw.tobytes())
+            f.write(b"\0" * (-raw.nbytes % BLOCK))
+    os.replace(tmp, path)
+    return path
 
 
 # ------------------------------------------------------------------------------- tables

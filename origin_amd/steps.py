@@ -865,6 +865,77 @@ class SimpleOrig:
             else:
                 self._bind(i, cls)
 
+    @classmethod
+    def from_cube(cls, cube, profiles, PSF, FWHM_PSF, LBDA_FWHM_PSF=None, wfields=None,
+                  FWHM_profiles=None, ctx=None, devices=None, backend=None, param=None):
+        """Step 0 of the reference (``ORIGIN.__init__``, origin.py:210-244): a session from the
+        path of a MUSE cube file.  The file's bytes go to HBM and one kernel leaves cube_raw, var
+        and mask there (``fitsio.read_cube``); ``cube_raw`` / ``var`` / ``mask`` of the session
+        are ``LazyCube``s over them (float64 / float64 / bool on demand, as the reference holds
+        them), ``ima_white`` the masked mean over z, ``wcs_header`` / ``wave_header`` the world
+        coordinates of the DATA header, which ``Step.dump`` writes back.
+
+        ``profiles``: the path of a dictionary (``fitsio.read_profiles``: fills ``FWHM_profiles``
+        too) or a list of arrays.  ``PSF``: a ``(Nz, P, P)`` array or the path of its file, or a
+        list of either with ``wfields`` (paths or ``(Ny, Nx)`` arrays), one per field of a mosaic;
+        checked as origin.py:619-628.  ``FWHM_PSF``: in pixels, one per field.  Building the FSF
+        from the ``FSF*`` keywords of the cube's header (``PSF=None`` in the reference) is
+        mpdaf's ``FSFModel`` and is not here.  ``param['cubename']``, ``['profiles']`` and
+        ``['PSF']`` record the paths.  With ``devices`` the tiled session takes the host arrays
+        from the ``LazyCube``s, as it takes arrays."""
+        info = fitsio.open_cube(cube)
+        if PSF is None:
+            raise ValueError(
+                "PSF=None: building the FSF from the FSF* keywords of the cube header is mpdaf's "
+                "FSFModel and is not part of origin_amd; give the PSF cube(s) and FWHM_PSF")
+        Nz, Ny, Nx = info.shape
+        param = dict(param or {})
+        param['cubename'] = cube
+        param['profiles'] = profiles if isinstance(profiles, str) else None
+        if isinstance(profiles, str):
+            profiles, fwhm = fitsio.read_profiles(profiles)
+            FWHM_profiles = fwhm if FWHM_profiles is None else FWHM_profiles
+        elif len({np.asarray(p).shape[0] for p in profiles}) != 1:
+            raise ValueError("The profiles must have the same size")
+
+        def host(a):
+            return fitsio.read_host_image(a) if isinstance(a, str) else np.asarray(a)
+
+        def check_psf(psf):
+            if psf.ndim != 3 or psf.shape[1] != psf.shape[2]:
+                raise ValueError("PSF must be a square image.")
+            if not psf.shape[1] % 2:
+                raise ValueError("The spatial size of the PSF must be odd.")
+            if psf.shape[0] != Nz:
+                raise ValueError("PSF and data cube have not the same dimensions along the "
+                                 "spectral axis.")
+            return psf
+
+        if isinstance(PSF, (list, tuple)):
+            if wfields is None or len(wfields) != len(PSF):
+                raise ValueError("a list of PSFs needs one weight map (wfields) per field")
+            param['PSF'] = list(PSF) if all(isinstance(p, str) for p in PSF) else None
+            PSF = [check_psf(host(p)) for p in PSF]
+            wfields = [host(w) for w in wfields]
+            for w in wfields:
+                if w.shape != (Ny, Nx):
+                    raise ValueError(f"weight map {w.shape} for a field of {(Ny, Nx)}")
+            FWHM_PSF = list(np.atleast_1d(FWHM_PSF))
+        else:
+            param['PSF'] = PSF if isinstance(PSF, str) else None
+            PSF, wfields = check_psf(host(PSF)), None
+            FWHM_PSF = float(np.mean(FWHM_PSF))
+        ctx = ctx or default_context(0 if not devices else int(devices[0]))
+        raw, var, mask, ima_white, wcs, wave = fitsio.read_cube(cube, ctx)
+        orig = cls(LazyCube(raw), LazyCube(var), LazyCube(mask, dtype=bool), PSF, profiles,
+                   FWHM_PSF=FWHM_PSF, wfields=wfields, param=param, ctx=ctx, devices=devices,
+                   backend=backend, FWHM_profiles=FWHM_profiles)
+        orig.LBDA_FWHM_PSF = LBDA_FWHM_PSF
+        orig.ima_white, orig.wcs_header, orig.wave_header = ima_white, wcs, wave
+        if _session_of(orig) is None:      # where _inputs_on_device looks for them
+            _cache(orig).update(raw=raw, var=var, mask=mask)
+        return orig
+
     def _bind(self, idx, cls):
         step = cls(self, idx, self.param)
         self.steps[step.name] = step
@@ -898,6 +969,8 @@ class SimpleOrig:
     @property
     def shape(self):
         """(Nz, Ny, Nx) of the processed cube."""
+        if isinstance(self.cube_raw, LazyCube):      # (no host copy for a shape)
+            return tuple(self.cube_raw.shape)
         return tuple(getattr(self.cube_raw, '_data', self.cube_raw).shape)
 
     # the thresholds of step 6, overridden by step 7's keywords (origin.py:496-513)
