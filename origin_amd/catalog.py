@@ -25,13 +25,14 @@ from datetime import datetime
 
 import numpy as np
 
-from . import kernels
+from . import cubes
 
 NOT_MERGED = -9999
 STAT_COLUMNS = ("flux", "STD", "nsigSTD", "T_GLR", "nsigTGLR", "purity")
 
 
 def _columns(tbl):
+    """Any table-like (an astropy Table, a dict of columns) as an OrderedDict of NumPy columns."""
     names = tbl.colnames if hasattr(tbl, "colnames") else list(tbl.keys())
     return OrderedDict((k, np.asarray(tbl[k])) for k in names)
 
@@ -150,11 +151,8 @@ def add_tglr_stat(src, lines, std_correl, std_std):
 
 
 def cube_std(ctx, cube):
-    """``np.std`` of a cube in HBM: ``kernels.cube_std`` for a DeviceArray; cubes that live in
-    pieces on several devices (session.TiledCube) bring their own."""
-    if hasattr(cube, "std"):
-        return cube.std()
-    return kernels.cube_std(ctx, cube)
+    """``np.std`` of a cube in any of its forms (``cubes.resident``) as a reduction in HBM."""
+    return cubes.std(cubes.resident(ctx, cube))
 
 
 def clean_results(ctx, cat2, cube_correl, cube_std_, merge_lines_z_threshold=5):
@@ -172,8 +170,6 @@ def from_session(orig, cat2=None, merge_lines_z_threshold=5):
     """``clean_results`` on what a session holds: ``orig.Cat2`` unless given, and the cube_correl
     and cube_std that steps 5 and 1 left in HBM (read back from their files through the device-side
     FITS decoder when the session was dumped)."""
-    from .steps import _HipStepMixin, _ctx_of
-    ctx = _ctx_of(orig)
-    get = _HipStepMixin()._get_cube
-    return clean_results(ctx, orig.Cat2 if cat2 is None else cat2, get(orig, ctx, "cube_correl"),
-                         get(orig, ctx, "cube_std"), merge_lines_z_threshold)
+    return clean_results(cubes.ctx_of(orig), orig.Cat2 if cat2 is None else cat2,
+                         cubes.session_cube(orig, "cube_correl"),
+                         cubes.session_cube(orig, "cube_std"), merge_lines_z_threshold)

@@ -17,7 +17,7 @@ Tables are plain dicts of NumPy columns (astropy is not a dependency of this pac
 """
 import numpy as np
 
-from . import kernels
+from . import cubes, kernels
 
 CAT0_COLUMNS = ("x0", "y0", "z0", "comp", "STD", "T_GLR", "profile")
 
@@ -25,29 +25,23 @@ CAT0_COLUMNS = ("x0", "y0", "z0", "comp", "STD", "T_GLR", "profile")
 def det_correl_min(ctx, cube_local_min, thresh):
     """``Detection.det_correl_min`` (steps.py:935-939): positions above ``thresh`` in
     cube_local_min -> (zm, ym, xm)."""
-    w = _where_above(ctx, cube_local_min, thresh)
+    w = cubes.where_above(cubes.resident(ctx, cube_local_min), thresh)
     return w["z"], w["y"], w["x"]
-
-
-def _where_above(ctx, cube, threshold, aux=None):
-    """``kernels.where_above`` for a DeviceArray; cubes that live in pieces on several devices
-    (session.TiledCube) bring their own."""
-    if hasattr(cube, "where_above"):
-        return cube.where_above(threshold, aux=aux)
-    return kernels.where_above(ctx, cube, threshold, aux=aux)
 
 
 def threshold_detections(ctx, cube_local_max, cube_profile, cube_std_local_max,
                          threshold_correl, threshold_std, maxdist_lines=2.5):
-    """The first half of ``Detection.run`` (steps.py:956-994) on device cubes.
+    """The first half of ``Detection.run`` (steps.py:956-994) on cubes in any form
+    ``cubes.resident`` takes; ``cube_profile`` (uint8) in the form of ``cube_local_max``.
 
     Returns ``(cat0, cat_correl, cat_std_kept)``: ``cat0`` the raw detection table (correl
     rows, then std rows: the ``vstack`` of :981), ``cat_correl`` its correl rows and
     ``cat_std_kept`` the std rows farther than ``maxdist_lines`` from every correl detection
     (:983-994; in ascending row order) -- the two tables the reference stacks again at :1010.
     """
-    c = _where_above(ctx, cube_local_max, threshold_correl, aux=cube_profile)
-    s = _where_above(ctx, cube_std_local_max, threshold_std)
+    c = cubes.where_above(cubes.resident(ctx, cube_local_max), threshold_correl,
+                          aux=cubes.resident(ctx, cube_profile, np.uint8))
+    s = cubes.where_above(cubes.resident(ctx, cube_std_local_max), threshold_std)
     n, m = c["z"].size, s["z"].size
     cat = dict(x0=c["x"], y0=c["y"], z0=c["z"], comp=np.zeros(n, int), STD=np.full(n, np.nan),
                T_GLR=c["value"], profile=c["aux"])
@@ -62,16 +56,14 @@ def from_session(orig, threshold=None, threshold_std=None, maxdist_lines=2.5):
     """``threshold_detections`` on the cubes a session holds (device copies left by steps 1 and
     5 when there are any, host cubes uploaded otherwise) with the thresholds of step 6
     (``param['threshold']``, ``param['threshold_std']``) unless given, like steps.py:951-954."""
-    from .steps import _HipStepMixin, _ctx_of
-    ctx = _ctx_of(orig)
-    get = _HipStepMixin()._get_cube
+    ctx = cubes.ctx_of(orig)
     thr = orig.param['threshold'] if threshold is None else threshold
     thr_std = orig.param['threshold_std'] if threshold_std is None else threshold_std
-    prof = get(orig, ctx, 'cube_profile')
-    if prof.dtype != np.uint8 and not hasattr(prof, "where_above"):
-        prof = ctx.to_device(prof.to_host().astype(np.uint8))
-    return threshold_detections(ctx, get(orig, ctx, 'cube_local_max'), prof,
-                                get(orig, ctx, 'cube_std_local_max'), thr, thr_std,
+    prof = cubes.session_cube(orig, 'cube_profile', np.uint8)
+    if prof.dtype != np.uint8:     # (a device copy somebody made with another element type)
+        prof = ctx.to_device(cubes.host_array(prof).astype(np.uint8))
+    return threshold_detections(ctx, cubes.session_cube(orig, 'cube_local_max'), prof,
+                                cubes.session_cube(orig, 'cube_std_local_max'), thr, thr_std,
                                 maxdist_lines)
 
 
@@ -141,7 +133,7 @@ def make_cat1(ctx, cat_correl, cat_std_kept, segmap_label, Pval, Pval_comp, tol_
     inside one ``ID`` by input row."""
     cat = {k: np.concatenate([np.asarray(cat_correl[k]), np.asarray(cat_std_kept[k])])
            for k in CAT0_COLUMNS}
-    seg = np.asarray(getattr(segmap_label, "_data", segmap_label))
+    seg = cubes.host_array(segmap_label)
     cat["area"] = seg[cat["y0"], cat["x0"]]
     shape = None
     if len(cat["z0"]):
@@ -170,8 +162,7 @@ def cat1_from_session(orig, segmap_label=None, tol_spat=3, tol_spec=5, threshold
     and ``orig.wave``: the ``Cat1`` of ``Detection.run``.  ``segmap_label=None`` uses
     ``orig.segmap_cont`` as it is: the reference's extra ``phot_deblend_sources`` pass over it
     (steps.py:1006) needs photutils and stays with the caller, who passes its result here."""
-    from .steps import _ctx_of
     _, cat, cat_std = from_session(orig, threshold, threshold_std, maxdist_lines)
     seg = orig.segmap_cont if segmap_label is None else segmap_label
-    return make_cat1(_ctx_of(orig), cat, cat_std, seg, orig.Pval, orig.Pval_comp, tol_spat,
+    return make_cat1(cubes.ctx_of(orig), cat, cat_std, seg, orig.Pval, orig.Pval_comp, tol_spat,
                      tol_spec, getattr(orig, "wcs", None), getattr(orig, "wave", None))

@@ -25,7 +25,7 @@ from collections import OrderedDict, namedtuple
 
 import numpy as np
 
-from . import _capi
+from . import _capi, cubes     # (cubes imports this module too: only names used at call time)
 from .device import DeviceArray, default_context
 
 BLOCK = 2880
@@ -180,14 +180,11 @@ def scan(path):
 # ------------------------------------------------------------------------------- writing
 def _device_source(ctx, data):
     """(DeviceArray, host dtype the reference would hold) for anything a DataObj may hold."""
-    dev = getattr(data, "dev", None)
-    if dev is not None:  # steps.LazyCube
-        if hasattr(dev, "gathered"):   # in pieces on several devices (session.TiledCube)
-            return dev.gathered(ctx), np.dtype(getattr(data, "_dtype", dev.dtype))
-        return dev, np.dtype(getattr(data, "_dtype", dev.dtype))
-    if isinstance(data, DeviceArray):
-        return data, data.dtype
-    host = np.asarray(getattr(data, "_data", data))
+    lazy = isinstance(data, cubes.LazyCube) and data.dev is not None
+    if lazy or isinstance(data, (DeviceArray, cubes.CubeForm)):
+        dev = cubes.dense(ctx, data)
+        return dev, np.dtype(data._dtype) if lazy else dev.dtype
+    host = cubes.host_array(data)
     ref_dtype = host.dtype
     if host.dtype == bool:
         host = host.astype(np.uint8)
@@ -238,7 +235,7 @@ def write_image(path, data, name="DATA", header=None, bitpix=None, ctx=None,
     mpdaf's ``DataArray.write`` for an object without variance or mask, which is what
     ``Step.store_cube`` / ``store_image`` create (steps.py:284-299, mask=nomask).
 
-    ``data``: DeviceArray, steps.LazyCube or anything array-like (uploaded).  ``bitpix``
+    ``data``: any form ``cubes.dense`` takes (host data is uploaded).  ``bitpix``
     defaults to the FITS type of the dtype the reference would hold (float64 -> -64 as with
     ``convert_float32=False``)."""
     ctx = ctx or default_context(0)
@@ -324,10 +321,6 @@ class FitsCube:
         return self._host
 
     data = _data
-
-    @property
-    def dev(self):
-        return None
 
     def device(self, ctx, dtype=np.float32):
         key = np.dtype(dtype)

@@ -396,16 +396,20 @@ def std_from_moments(n, m2):
     return float(np.sqrt(m2 / n)) if n > 0 else float("nan")
 
 
-def cube_std(ctx, cube, keep=None):
-    """``np.std(cube)`` of a float32 device cube (over the kept spaxels) in NumPy's own two-pass
-    form (lib_origin.py:2127-2129): the first pass gives the mean, the second the sum of squared
-    deviations from it.  Not ``sum x^2 - (sum x)^2 / n``: that loses the digits a cube with a
-    mean far from 0 needs."""
-    n, s1, _ = cube_moments(ctx, cube, 0.0, keep)
+def two_pass_std(moments):
+    """``np.std`` in NumPy's own two-pass form (lib_origin.py:2127-2129) over ``moments(shift)
+    -> (n, s1, s2)``: the first pass gives the mean, the second the sum of squared deviations
+    from it.  Not ``sum x^2 - (sum x)^2 / n``: that loses the digits a cube with a mean far from
+    0 needs."""
+    n, s1, _ = moments(0.0)
     if n == 0:
         return float("nan")
-    _, _, m2 = cube_moments(ctx, cube, s1 / n, keep)
-    return std_from_moments(n, m2)
+    return std_from_moments(n, moments(s1 / n)[2])
+
+
+def cube_std(ctx, cube, keep=None):
+    """``np.std(cube)`` of a float32 device cube (over the kept spaxels): ``two_pass_std``."""
+    return two_pass_std(lambda shift: cube_moments(ctx, cube, shift, keep))
 
 
 # ------------------------------------------------------------------------- line estimation

@@ -13,9 +13,12 @@ outputs are host ``ndarray`` s (float64 out, as the reference produces); interna
 cubes are float32 in HBM.  There is no CPU fallback: without the library or a GPU every
 function raises.
 """
+import logging
+
 import numpy as np
 
-from . import kernels
+from . import catalog, cubes, detection, kernels, lines, sparse
+from .catalog import _columns
 from .device import default_context
 from .pca import GreedyPCA
 from .thresholds import compute_thresh_gaussfit
@@ -38,10 +41,8 @@ def _ctx():
     return default_context(0)
 
 
-def _mask_u8(mask, shape):
-    if mask is None or mask is np.ma.nomask:
-        return np.zeros(shape, dtype=np.uint8)
-    return np.ascontiguousarray(np.broadcast_to(mask, shape), dtype=np.uint8)
+def _mask_on_device(ctx, mask, shape):
+    return ctx.to_device(np.broadcast_to(cubes.host_mask(mask, shape), shape), np.uint8)
 
 
 def dct_residual(w_raw, order, var, approx, mask):
@@ -51,7 +52,7 @@ def dct_residual(w_raw, order, var, approx, mask):
     shape = w_raw.shape
     raw = ctx.to_device(w_raw, np.float32)
     dvar = ctx.to_device(np.broadcast_to(var, shape), np.float32)
-    dmask = ctx.to_device(_mask_u8(mask, shape))
+    dmask = _mask_on_device(ctx, mask, shape)
     coef = kernels.dct_fit(ctx, raw, dvar, dmask, order, approx)
     cont = kernels.dct_continuum(ctx, coef, shape[0])
     return cont.to_host_f64()
@@ -129,8 +130,7 @@ def compute_local_max(correl, correl_min, mask, size=3):
     correl = np.asarray(correl)
     dc = ctx.to_device(correl, np.float32)
     dm = dc if correl_min is correl else ctx.to_device(correl_min, np.float32)
-    dmask = ctx.to_device(_mask_u8(mask, correl.shape))
-    from . import sparse
+    dmask = _mask_on_device(ctx, mask, correl.shape)
     # (sparse pass where it exists: only the maxima cross PCIe, the zeros are made on the host)
     lmax, lmin = sparse.local_max(ctx, dc, dm, dmask, size)
     return lmax.to_host_f64(), lmin.to_host_f64()
@@ -153,38 +153,13 @@ class PurityTable(dict):
 
 def Compute_threshold_purity(purity, cube_local_max, cube_local_min, segmap=None,
                              threshlist=None):
-    """Threshold for a given purity (reference lib_origin.py:1391-1479).  The cubes may be host
-    arrays or float32 ``DeviceArray`` s (no PCIe traffic then); only per-spaxel maxima and the
-    counts per threshold leave the GPU.  Returns (threshold, PurityTable)."""
-    import logging
-
-    from .device import DeviceArray
+    """Threshold for a given purity (reference lib_origin.py:1391-1479).  The cubes may come in
+    any form ``cubes.resident`` takes (host arrays are uploaded as float32; no PCIe traffic for
+    what is in HBM already); only per-spaxel maxima and the counts per threshold leave the GPU.
+    Returns (threshold, PurityTable)."""
     ctx = _ctx()
     logger = logging.getLogger(__name__)
-
-    class OnDevice:
-        """The two reductions on one DeviceArray; cubes that live in pieces on several devices
-        (session.TiledCube) bring their own ``zmax_map`` / ``count_above``."""
-
-        def __init__(self, a):
-            self.a, self.shape = a, a.shape
-
-        def _keep(self, keep):
-            return None if keep is None else ctx.to_device(
-                np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1))
-
-        def zmax_map(self, keep=None):
-            return kernels.zmax_map(ctx, self.a, self._keep(keep))
-
-        def count_above(self, thresholds, keep=None):
-            return kernels.count_above(ctx, self.a, thresholds, self._keep(keep))
-
-    def dev(c):
-        if hasattr(c, "count_above"):
-            return c
-        return OnDevice(c if isinstance(c, DeviceArray) else ctx.to_device(np.asarray(c), np.float32))
-
-    lmax, lmin = dev(cube_local_max), dev(cube_local_min)
+    lmax, lmin = cubes.resident(ctx, cube_local_max), cubes.resident(ctx, cube_local_min)
     L1 = int(np.prod(lmin.shape[1:]))                                          # :1425
     keep = None
     if segmap is not None:                                                     # :1428-1435
@@ -194,13 +169,13 @@ def Compute_threshold_purity(purity, cube_local_max, cube_local_min, segmap=None
     else:
         L0 = L1
     if threshlist is None:                                                     # :1437-1442
-        map_max = lmax.zmax_map()
-        threshmax = min(lmin.zmax_map(keep).max(), map_max.max())
+        map_max = cubes.zmax_map(lmax)
+        threshmax = min(cubes.zmax_map(lmin, keep).max(), map_max.max())
         threshmin = np.median(map_max) * 1.1
         threshlist = np.linspace(threshmin, threshmax, 50)
     threshlist = np.asarray(threshlist, dtype=np.float64)
-    n1 = lmax.count_above(threshlist)                                          # :1444-1450
-    n0 = lmin.count_above(threshlist, keep) * (L1 / L0)                        # :1452
+    n1 = cubes.count_above(lmax, threshlist)                                   # :1444-1450
+    n0 = cubes.count_above(lmin, threshlist, keep) * (L1 / L0)                 # :1452
     with np.errstate(divide='ignore', invalid='ignore'):
         est_purity = 1 - n0 / n1                                               # :1454
     order = np.argsort(threshlist, kind='stable')                              # res.sort('Tval_r')
@@ -227,13 +202,10 @@ def estimation_line(Cat1, raw, var, psf, wght, wcs, wave, size_grid=1, criteria=
     columns); ``Cat2`` is a dict of NumPy columns in the reference's column order.  ``wcs`` /
     ``wave`` are used only if not None: ``ra``, ``dec`` and ``lbda`` are then set from the new
     positions (:1922-1925).  Deviations from the reference: see ``origin_amd.lines``."""
-    from . import lines
     lines.check_arguments(wght, size_grid, criteria)
     ctx = _ctx()
-    names = Cat1.colnames if hasattr(Cat1, 'colnames') else list(Cat1.keys())
-    cat = {k: np.asarray(Cat1[k]) for k in names}
-    raw = np.asarray(getattr(raw, '_data', raw))
-    var = np.asarray(getattr(var, '_data', var))
+    cat = _columns(Cat1)
+    raw, var = cubes.host_array(raw), cubes.host_array(var)
     d_raw = ctx.to_device(raw, np.float32)
     d_var = ctx.to_device(np.broadcast_to(var, raw.shape), np.float32)
     cat2, lin_est, var_est = lines.estimate_lines(ctx, cat, d_raw, d_var, psf, wght, size_grid,
@@ -246,11 +218,6 @@ def estimation_line(Cat1, raw, var, psf, wght, wcs, wave, size_grid=1, criteria=
     return cat2, lin_est, var_est
 
 
-def _columns(tbl):
-    names = tbl.colnames if hasattr(tbl, 'colnames') else list(tbl.keys())
-    return {k: np.asarray(tbl[k]) for k in names}
-
-
 # The two functions below keep the reference's signatures but return dicts of NumPy columns, as
 # estimation_line does.  They are not in __all__: Detection.run goes on with astropy Table
 # methods on what spatiospectral_merging returns, so swapping them into muse_origin.steps
@@ -260,14 +227,12 @@ def spatiospectral_merging(tbl, tol_spat, tol_spec):
     ``imatch``, ``imatch2``, rows sorted by ``imatch``) through ``detection.merge_detections``.
     ``tbl``: any table-like with ``x0``, ``y0``, ``z0``, ``area`` (an astropy Table, a dict of
     columns).  Rows of one ``imatch`` come in input order."""
-    from . import detection
     return detection.merge_detections(_ctx(), _columns(tbl), tol_spat, tol_spec)
 
 
 def purity_estimation(cat, Pval, Pval_comp):
     """``cat`` (``comp``, ``T_GLR``, ``STD``) as a dict of columns with the ``purity`` column of
     the reference (lib_origin.py:1941-1991) added.  Host arithmetic (scipy ``interp1d``)."""
-    from . import detection
     out = _columns(cat)
     out['purity'] = detection.purity_estimation(out, Pval, Pval_comp)
     return out
@@ -279,35 +244,20 @@ def purity_estimation(cat, Pval, Pval_comp):
 def merge_similar_lines(table, *, z_pix_threshold=5):
     """The reference's table (lib_origin.py:2140-2222: the input rows sorted by ``(ID, z)`` with
     ``line_merged_flag`` and ``merged_in`` added) through ``catalog.merge_similar_lines``."""
-    from . import catalog
     return catalog.merge_similar_lines(_columns(table), z_pix_threshold=z_pix_threshold)
 
 
 def unique_sources(table):
     """One row per ``ID`` (lib_origin.py:1994-2091) through ``catalog.unique_sources``."""
-    from . import catalog
     return catalog.unique_sources(_columns(table))
 
 
 def add_tglr_stat(src_table, lines_table, correl, std):
     """``add_tglr_stat`` (lib_origin.py:2094-2137): ``lines_table`` gains ``nsigTGLR`` and
     ``nsigSTD`` in place, the returned source table the per-``ID`` maxima.  ``correl`` / ``std``
-    may be host arrays (uploaded as float32), float32 ``DeviceArray`` s, ``LazyCube`` s or cubes
-    tiled over several devices: their standard deviations are reductions on the device
-    (``kernels.cube_std``), only the two scalars come back."""
-    from . import catalog
-    from .device import DeviceArray
+    may come in any form ``cubes.resident`` takes (host arrays are uploaded as float32): their
+    standard deviations are reductions on the device (``cubes.std``), only the two scalars come
+    back."""
     ctx = _ctx()
-
-    def sigma(c):
-        if isinstance(c, DeviceArray):
-            return kernels.cube_std(ctx, c)
-        if not isinstance(c, np.ndarray):
-            if hasattr(c, 'std'):                                    # session.TiledCube
-                return c.std()
-            if hasattr(c, 'device'):                                 # LazyCube, FitsCube
-                return kernels.cube_std(ctx, c.device(ctx, np.float32))
-        return kernels.cube_std(ctx, ctx.to_device(np.asarray(getattr(c, '_data', c)),
-                                                   np.float32))
-
-    return catalog.add_tglr_stat(_columns(src_table), lines_table, sigma(correl), sigma(std))
+    return catalog.add_tglr_stat(_columns(src_table), lines_table,
+                                 catalog.cube_std(ctx, correl), catalog.cube_std(ctx, std))

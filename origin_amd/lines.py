@@ -25,7 +25,7 @@ Deviations from the reference:
 """
 import numpy as np
 
-from . import kernels
+from . import cubes, kernels
 
 NEW_COLUMNS = ("x", "y", "z", "residual", "flux", "num_line")
 CRITERIA = ("flux", "mse")
@@ -82,7 +82,6 @@ def from_session(orig, cat1, grid_dxy=0):
     'flux', order_dct 30, horiz_psf 1, horiz 5) on what a session holds: the device copies of
     cube_raw and var that step 1 uploaded (uploaded now otherwise), ``orig.PSF`` and
     ``orig.wfields``."""
-    from .steps import _ctx_of, _inputs_on_device
-    ctx = _ctx_of(orig)
-    raw, var, _ = _inputs_on_device(orig, ctx)
+    ctx = cubes.ctx_of(orig)
+    raw, var, _ = cubes.inputs_on_device(orig, ctx)
     return estimate_lines(ctx, cat1, raw, var, orig.PSF, orig.wfields, size_grid=grid_dxy)

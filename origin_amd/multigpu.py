@@ -27,7 +27,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _capi, kernels, sparse
+from . import _capi, cubes, kernels, sparse
 from .device import copy_box
 
 Tile = namedtuple("Tile", "rank ty tx y0 y1 x0 x1")   # ty: row band, tx: position in the band
@@ -236,7 +236,7 @@ class OwnerTiling(Partition):
         steps.py:560-563: cube_faint keeps cube_std there, lib_origin.py:799) goes with the
         nearest labelled spaxel."""
         from scipy import ndimage as ndi
-        amap = np.asarray(getattr(areamap, "_data", areamap)).astype(np.int64)
+        amap = cubes.host_array(areamap).astype(np.int64)
         labels = np.unique(amap)
         labels = labels[labels > 0]
         if len(labels) < world:

@@ -35,7 +35,7 @@ import threading
 
 import numpy as np
 
-from . import _capi, kernels, multigpu, pipeline, sparse
+from . import cubes, kernels, multigpu, pipeline, sparse
 from .device import Context, DeviceArray, copy_box
 from .pca import GreedyPCA
 
@@ -185,12 +185,13 @@ class DeviceGroup:
 
 
 # ------------------------------------------------------------------------------- cubes
-class TiledCube:
+class TiledCube(cubes.CubeForm):
     """A cube of the field that lives in pieces on the ranks' devices.  ``parts[r]`` =
-    (DeviceArray a, (by, bx), (y0, y1, x0, x1), owned): the box of ``a`` that starts at (by, bx)
-    covers the field window [y0:y1, x0:x1]; ``owned`` (bool (y1-y0, x1-x0) or None = all) marks
-    the spaxels of that window that are this part's.  Reads like a DeviceArray where the Step
-    seam needs one (``shape``, ``dtype``, ``to_host``, ``to_host_f64``)."""
+    (a, (by, bx), (y0, y1, x0, x1), owned) with ``a`` a DeviceArray or a sparse.SparseCube on
+    rank r's context: the box of ``a`` that starts at (by, bx) covers the field window [y0:y1,
+    x0:x1]; ``owned`` (bool (y1-y0, x1-x0) or None = all) marks the spaxels of that window that
+    are this part's.  Reads like a DeviceArray where the Step seam needs one (``shape``,
+    ``dtype``, ``to_host``, ``to_host_f64``)."""
 
     def __init__(self, group, shape, dtype, parts):
         self.group, self.shape, self.dtype, self.parts = group, tuple(shape), np.dtype(dtype), parts
@@ -215,19 +216,20 @@ class TiledCube:
         def one(rank):
             a, crop, window, put = self._part(rank)
             box = tuple(c.stop - c.start for c in crop)
-            # (sparse.SparseCube: zeros + its entries, on the host)
-            if hasattr(a, "entries") or len(self.shape) == 2 or a.shape[1:] == box:
-                blk = a.to_host()[(..., *crop)]
-            else:
+            # (a sparse.SparseCube reads back as zeros + its entries, made on the host)
+            crop_on_device = (isinstance(a, DeviceArray) and len(self.shape) == 3
+                              and a.shape[1:] != box)
+            if crop_on_device:
                 # the part's box as one contiguous block: crop on the device (one strided copy
                 # kernel), then one large copy through pinned staging -- a strided device-to-host
                 # copy is one hipMemcpy2D per channel
-                ctx = self.group.ctxs[rank]
-                tmp = ctx.empty((a.shape[0],) + box, a.dtype)
-                copy_box(ctx, tmp, tmp.shape, (0, 0, 0), a, a.shape, (0, crop[0].start,
-                                                                      crop[1].start), tmp.shape)
+                tmp = a.ctx.empty((a.shape[0],) + box, a.dtype)
+                copy_box(a.ctx, tmp, tmp.shape, (0, 0, 0), a, a.shape, (0, crop[0].start,
+                                                                        crop[1].start), tmp.shape)
                 blk = tmp.to_host()
                 tmp.free()
+            else:
+                blk = a.to_host()[(..., *crop)]
             put(out[(..., *window)], blk, convert)
         self.group.run(one)
         return out
@@ -263,9 +265,7 @@ class TiledCube:
 
         def one(rank):
             a, crop, window, put = self._part(rank)
-            ctx = self.group.ctxs[rank]
-            full = a.zmax_map(None) if hasattr(a, "entries") else kernels.zmax_map(ctx, a, None)
-            m = full[crop]
+            m = cubes.zmax_map(a, None)[crop]
             if keep is not None:   # max_z (cube * keep) = keep ? max_z cube : 0
                 m = np.where(np.asarray(keep).reshape(self.shape[1:])[window] != 0, m, 0.0)
             put(out[window], m)
@@ -275,47 +275,27 @@ class TiledCube:
     def count_above(self, thresholds, keep=None):
         """counts[t] = #{kept voxels > thresholds[t]} over the whole field (int64)."""
         def one(rank):
-            ctx = self.group.ctxs[rank]
-            k = ctx.to_device(self._keep(rank, keep).reshape(-1))
-            a = self.parts[rank][0]
-            if hasattr(a, "entries"):
-                return a.count_above(thresholds, k)
-            return kernels.count_above(ctx, a, thresholds, k)
+            return cubes.count_above(self.parts[rank][0], thresholds, self._keep(rank, keep))
         return np.sum(self.group.run(one), axis=0)
 
-    def moments(self, shift=0.0):
+    def moments(self, shift=0.0, keep=None):
         """``(n, sum(x - shift), sum((x - shift)**2))`` over the whole field
         (kernels.cube_moments): each rank reduces its own part under the map of the spaxels it
-        owns, the host adds the triples in rank order."""
+        owns, the host adds the triples in rank order.  ``std()`` (cubes.CubeForm) makes its two
+        passes of it: the global mean of the first is the shift of the second on every rank."""
         def one(rank):
-            ctx = self.group.ctxs[rank]
-            k = ctx.to_device(self._keep(rank, None).reshape(-1))
-            a = self.parts[rank][0]
-            if hasattr(a, "entries"):
-                a = a.dense()
-            return kernels.cube_moments(ctx, a, shift, k)
+            return cubes.moments(self.parts[rank][0], shift, self._keep(rank, keep))
         n = s1 = s2 = 0.0
         for t in self.group.run(one):
             n, s1, s2 = n + t[0], s1 + t[1], s2 + t[2]
         return n, s1, s2
 
-    def std(self):
-        """``np.std`` of the stitched cube, two passes like ``kernels.cube_std``: the global mean
-        of the first pass is the shift of the second on every rank."""
-        n, s1, _ = self.moments(0.0)
-        if n == 0:
-            return float("nan")
-        return kernels.std_from_moments(n, self.moments(s1 / n)[2])
-
     def where_above(self, threshold, aux=None):
         """``np.where(cube > threshold)`` of the stitched cube, in NumPy's order, with the values
         (and those of the uint8 TiledCube ``aux`` with the same parts layout)."""
         def one(rank):
-            a = self.parts[rank][0]
-            ctx = self.group.ctxs[rank]
             ax = None if aux is None else aux.parts[rank][0]
-            w = (a.where_above(threshold, aux=ax) if hasattr(a, "entries")
-                 else kernels.where_above(ctx, a, threshold, aux=ax))
+            w = cubes.where_above(self.parts[rank][0], threshold, aux=ax)
             ok = self._keep(rank, None)[w["y"], w["x"]] != 0
             (by, bx), (y0, _, x0, _) = self.parts[rank][1:3]
             res = dict(z=w["z"][ok], y=w["y"][ok] - by + y0, x=w["x"][ok] - bx + x0,
@@ -376,9 +356,7 @@ class TiledSession:
     def distribute(self, host, tiling, name, dtype=np.float32):
         """A host (or TiledCube / DeviceArray) cube into per-rank tiles of ``tiling`` (the boxes;
         what other ranks own inside a box is there too, harmlessly)."""
-        if isinstance(host, TiledCube) or isinstance(host, DeviceArray):
-            host = host.to_host()
-        host = np.asarray(getattr(host, "_data", host))
+        host = cubes.host_array(host)
 
         def one(r):
             t = tiling.tile(r)
@@ -392,12 +370,9 @@ class TiledSession:
         host arrays of the whole field.  Returns the TiledCubes cube_std, cont_dct,
         cube_std_local_max / _min and the host images ima_std, ima_dct, o2 (O2 map of cube_std),
         cont_o2 (mean_z cont_dct^2)."""
-        raw = np.asarray(getattr(raw, "_data", raw))
-        var = np.asarray(getattr(var, "_data", var))
+        raw, var = cubes.host_array(raw), cubes.host_array(var)
         Nz, Ny, Nx = raw.shape
-        if mask is None or mask is np.ma.nomask:
-            mask = np.zeros(raw.shape, np.uint8)
-        mask = np.asarray(getattr(mask, "_data", mask))
+        mask = cubes.host_mask(mask, raw.shape)
         self.shape, self.host_mask = (Nz, Ny, Nx), mask
         halo = int(local_max_size) // 2
         p1 = self.p1 = multigpu.OwnerTiling.row_bands(Ny, Nx, self.world, halo)
@@ -435,7 +410,7 @@ class TiledSession:
 
     # -- step 4 --------------------------------------------------------------------
     def _areas(self, areamap, halo):
-        areamap = np.asarray(getattr(areamap, "_data", areamap)).astype(np.int64)
+        areamap = cubes.host_array(areamap).astype(np.int64)
         p2 = self.p2
         if p2 is None or p2.halo != halo or not np.array_equal(self._areamap, areamap):
             p2 = self.p2 = multigpu.OwnerTiling.from_areamap(areamap, self.world, halo)
@@ -506,8 +481,7 @@ class TiledSession:
                 and all("ext" in st and cube_faint.parts[r][0] is st["ext"]
                         for r, st in enumerate(self.rk)))
         if not mine:   # cube_faint from elsewhere (reloaded session): into the boxes' interiors
-            host = np.asarray(getattr(cube_faint, "_data", None) if hasattr(cube_faint, "_data")
-                              else cube_faint.to_host())
+            host = cubes.host_array(cube_faint)
         mask = getattr(self, "host_mask", None)
         self.group.attach()
 

@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, cubes, kernels
 from .device import DeviceArray
 
 NULL = C.c_void_p(0)
@@ -60,7 +60,6 @@ def local_max(ctx, correl, correl_min, mask, size=3, check=True):
     where it exists (size 3, Nx % 4 == 0, aligned cubes) -- ``check``: read the segment counts
     back (64 KB, one synchronisation) and fall back to the dense pass if a segment overflowed --,
     the dense kernels otherwise.  Returns two cubes: ``SparseCube`` s or float32 DeviceArrays."""
-    from . import kernels
     ok = (int(size) == 3 and correl.shape[2] % 4 == 0 and correl.ptr % 16 == 0
           and correl_min.ptr % 16 == 0 and (mask is None or mask.ptr % 4 == 0))
     if ok and plan(ctx, correl.shape)[0] > 0:
@@ -80,10 +79,10 @@ class SparseOverflow(RuntimeError):
     one voxel in 8): the caller runs the dense pass instead."""
 
 
-class SparseCube:
+class SparseCube(cubes.CubeForm):
     """One of the two cubes of a sparse local-maximum pass.  ``shape`` / ``dtype`` / ``to_host`` /
     ``to_host_f64`` read like a float32 DeviceArray's; ``count_above`` / ``zmax_map`` /
-    ``where_above`` are the reductions steps 6 and 7 make of it."""
+    ``where_above`` are the reductions steps 6 and 7 make of it, ``moments`` / ``std`` step 9's."""
 
     dtype = np.dtype(np.float32)
 
@@ -170,11 +169,8 @@ class SparseCube:
 
     # -- the consumers' reductions --------------------------------------------------------
     def _keep(self, keep):
-        if keep is None:
-            return NULL, None
-        k = keep if isinstance(keep, DeviceArray) else self.ctx.to_device(
-            np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1))
-        return k.p, k
+        k = cubes.keep_map(self.ctx, keep, self.shape[1] * self.shape[2])
+        return (NULL if k is None else k.p), k
 
     def count_above(self, thresholds, keep=None):
         """counts[t] = #{voxels (x keep) with value > thresholds[t]} (int64, host)."""
@@ -205,6 +201,10 @@ class SparseCube:
         _capi.call("origin_sparse_zmax_map", self.ctx.handle, *self._args(), kp, Ny * Nx, m.p)
         return m.to_host().astype(np.float64)
 
+    def moments(self, shift=0.0, keep=None):
+        """kernels.cube_moments of the dense cube (its zeros are voxels like the others)."""
+        return cubes.moments(self.dense(), shift, keep)
+
     def where_above(self, threshold, aux=None, cap=1 << 20):
         """``z, y, x = np.where(cube > threshold)`` in NumPy's order with the values (and those of
         the uint8 device cube ``aux``): kernels.where_above's contract."""
@@ -213,7 +213,6 @@ class SparseCube:
         if aux is not None and (aux.dtype != np.uint8 or tuple(aux.shape) != self.shape):
             raise ValueError("aux must be a uint8 device cube of the same shape")
         if not threshold >= 0:      # zeros qualify (or NaN: nothing does): the dense cube answers
-            from . import kernels
             return kernels.where_above(self.ctx, self.dense(), threshold, aux=aux, cap=cap)
         idx, val, ax = self._above(threshold, aux, cap)
         z, rem = np.divmod(idx, Ny * Nx)

@@ -33,54 +33,16 @@ import numpy as np
 from scipy import ndimage as ndi
 from scipy.signal import fftconvolve
 
-from . import fitsio, kernels, pipeline
-from .device import DeviceArray, default_context
+from . import catalog, cubes, detection, fitsio, kernels, lines, pipeline, sparse
+from .cubes import LazyCube, session_cube                         # noqa: F401 (LazyCube: re-export)
+from .cubes import cache as _cache, ctx_of as _ctx_of, inputs_on_device as _inputs_on_device
+from .device import default_context
+from .lib_origin import Compute_threshold_purity
 from .thresholds import compute_thresh_gaussfit
 
 __all__ = ('Preprocessing', 'CreateAreas', 'ComputePCAThreshold', 'ComputeGreedyPCA', 'ComputeTGLR',
            'ComputePurityThreshold', 'Detection', 'ComputeSpectra', 'CleanResults', 'Catalog',
            'Status', 'Step', 'DataObj', 'SimpleOrig', 'STEPS', 'register', 'unregister')
-
-
-# ----------------------------------------------------------------------------- containers
-class LazyCube:
-    """What a DataObj holds when mpdaf is absent: a device array plus an on-demand host
-    copy with the dtype the reference would have produced.  ``._data`` / ``.data`` mirror
-    the mpdaf attribute the ``run`` bodies read (e.g. steps.py:617, :688, :771)."""
-
-    def __init__(self, dev=None, host=None, dtype=np.float64):
-        self.dev, self._host, self._dtype = dev, host, dtype
-
-    @property
-    def _data(self):
-        if self._host is None:
-            self._host = (self.dev.to_host_f64() if self._dtype == np.float64
-                          else self.dev.to_host().astype(self._dtype, copy=False))
-        return self._host
-
-    data = _data
-
-    @property
-    def shape(self):
-        return self.dev.shape if self.dev is not None else self._host.shape
-
-    def device(self, ctx, dtype=np.float32):
-        if self.dev is None:
-            self.dev = ctx.to_device(self._host, dtype)
-        return self.dev
-
-
-def _wrap(ctx, value, dtype=np.float32):
-    """DeviceArray for anything cube-like a step may be handed (LazyCube, mpdaf object with
-    ``_data``, ndarray)."""
-    if isinstance(value, (LazyCube, fitsio.FitsCube)):
-        return value.device(ctx, dtype)
-    if isinstance(value, DeviceArray):
-        return value
-    if hasattr(value, "dense"):        # sparse.SparseCube
-        return value.dense()
-    data = getattr(value, "_data", value)
-    return ctx.to_device(np.asarray(data), dtype)
 
 
 # ----------------------------------------------------------------------------- framework
@@ -274,9 +236,8 @@ class Step:
                 if hasattr(obj, 'write'):  # astropy Table
                     obj.write(outf, overwrite=True)
                 else:
-                    fitsio.write_table(outf, OrderedDict(
-                        (c, obj[c]) for c in getattr(obj, 'colnames', obj)),
-                        header=getattr(obj, 'meta', None))
+                    fitsio.write_table(outf, catalog._columns(obj),
+                                       header=getattr(obj, 'meta', None))
             elif kind == 'array':
                 np.savetxt(outf, obj)
             elif kind == 'spectra':
@@ -322,24 +283,6 @@ def compute_segmap_gauss(data, pfa, fwhm_fsf=0, bins='fd'):
     return gamma, ndi.label(mask)[0]
 
 
-def _ctx_of(orig):
-    ctx = getattr(orig, 'hip_ctx', None)
-    if ctx is None:
-        ctx = default_context(0)
-        try:
-            orig.hip_ctx = ctx
-        except Exception:
-            pass
-    return ctx
-
-
-def _cache(orig):
-    c = orig.__dict__.get('_hip_cache')
-    if c is None:
-        c = orig.__dict__['_hip_cache'] = {}
-    return c
-
-
 # Devices of the sessions that do not say themselves (``register(devices=[...])`` sets it for
 # the reference's ORIGIN objects, which know nothing of GPUs); None = one context on device 0.
 _DEFAULT_DEVICES = None
@@ -362,24 +305,11 @@ def _session_of(orig):
     return sess
 
 
-def _inputs_on_device(orig, ctx):
-    """cube_raw / var / mask uploaded once per session (origin.py:262-274)."""
-    c = _cache(orig)
-    if 'raw' not in c:
-        c['raw'] = _wrap(ctx, orig.cube_raw)
-        c['var'] = _wrap(ctx, orig.var)
-        m = orig.mask
-        m = np.zeros(c['raw'].shape, np.uint8) if m is None or m is np.ma.nomask else m
-        # (a bool mask goes up as it is: one byte of 0 / 1 per voxel, no host-side copy)
-        c['mask'] = _wrap(ctx, np.asarray(m), np.uint8)
-    return c['raw'], c['var'], c['mask']
-
-
 # ----------------------------------------------------------------------------- run bodies
 class _HipStepMixin:
-    """Store / fetch cubes so that they stay in HBM between steps.  Under the stand-alone
-    ``Step`` the DataObj holds a ``LazyCube``; under the reference's ``Step`` (register())
-    ``store_cube`` builds an mpdaf Cube from a host array as usual."""
+    """Store cubes so that they stay in HBM between steps (``cubes.session_cube`` fetches them).
+    Under the stand-alone ``Step`` the DataObj holds a ``LazyCube``; under the reference's
+    ``Step`` (register()) ``store_cube`` builds an mpdaf Cube from a host array as usual."""
 
     def _put_cube(self, orig, name, dev, dtype=np.float64):
         _cache(orig)[name] = dev
@@ -388,12 +318,6 @@ class _HipStepMixin:
         else:
             self.store_cube(name, dev.to_host_f64() if dtype == np.float64
                             else dev.to_host().astype(dtype, copy=False))
-
-    def _get_cube(self, orig, ctx, name):
-        dev = _cache(orig).get(name)
-        if dev is not None:
-            return dev
-        return _wrap(ctx, getattr(orig, name))
 
 
 class _PreprocessingRun(_HipStepMixin):
@@ -418,7 +342,6 @@ class _PreprocessingRun(_HipStepMixin):
             out = pipeline.preprocess(ctx, raw, var, mask, dct_order, dct_approx,
                                       allreduce=getattr(orig, 'allreduce', None))
             ima_std = out['ima_std'].to_host().astype(np.float64)
-            from . import sparse
             lmax, lmin = sparse.local_max(ctx, out['cube_std'], out['cube_std'], mask,
                                           local_max_size)
             ima_dct, o2 = out['ima_dct'].to_host(), out['o2_host']
@@ -457,7 +380,7 @@ class _CreateAreasRun:
 
     def run(self, orig, pfa=0.2, minsize=100, maxsize=None):
         from .areas import create_areamap
-        mask = np.asarray(getattr(orig.mask, '_data', orig.mask), dtype=bool)
+        mask = _data(orig.mask).astype(bool, copy=False)
         nexp = int(np.sum(mask.shape[0] - mask.sum(axis=0) > 0))
         nsub = np.maximum(1, int(np.sqrt(nexp / (minsize ** 2))))
         if nsub > 1:
@@ -471,7 +394,7 @@ class _CreateAreasRun:
     def set_areamap(self, areamap):
         """Use an area map made elsewhere (a regular grid in the benchmarks, a map loaded from a
         previous session) instead of running the step: same outputs and status as ``run``."""
-        areamap = np.asarray(getattr(areamap, '_data', areamap)).astype(int)
+        areamap = _data(areamap).astype(int)
         labels = np.unique(areamap)
         self.orig.param['nbareas'] = len(labels) - (1 if 0 in labels else 0)
         self.store_image('areamap', areamap)
@@ -487,8 +410,8 @@ class _ComputePCAThresholdRun(_HipStepMixin):
         o2 = _cache(orig).get('o2_std')
         if o2 is None:  # session reloaded: recompute the O2 map from cube_std
             ctx = _ctx_of(orig)
-            o2 = kernels.o2test(ctx, self._get_cube(orig, ctx, 'cube_std')).to_host()
-        areamap = getattr(orig.areamap, '_data', orig.areamap)
+            o2 = kernels.o2test(ctx, cubes.dense(ctx, session_cube(orig, 'cube_std'))).to_host()
+        areamap = _data(orig.areamap)
         res = pipeline.pca_threshold(o2, areamap, orig.nbAreas, pfa_test)
         for i in range(orig.nbAreas):
             self._loginfo('Area %d, estimation mean/std/threshold: %f/%f/%f', i + 1,
@@ -508,7 +431,7 @@ class _ComputeGreedyPCARun(_HipStepMixin):
         orig.param['threshold_list'] = thr
         self._loginfo('   - List of threshold = %s', ' '.join("%.2f" % x for x in thr))
         self._loginfo('Compute greedy PCA on each zone')
-        areamap = getattr(orig.areamap, '_data', orig.areamap)
+        areamap = _data(orig.areamap)
         sess = _session_of(orig)
         if sess is not None:   # several devices: whole areas per rank (session.TiledSession)
             std = _cache(orig).get('cube_std')
@@ -519,7 +442,7 @@ class _ComputeGreedyPCARun(_HipStepMixin):
                 itermax)
         else:
             faint, mapO2, nstop, drv = pipeline.greedy_pca(
-                ctx, self._get_cube(orig, ctx, 'cube_std'), areamap, orig.nbAreas, thr,
+                ctx, cubes.dense(ctx, session_cube(orig, 'cube_std')), areamap, orig.nbAreas, thr,
                 orig.testO2, Noise_population, itermax)
         if nstop > 0:
             self._logwarning('The iterations have been reached the limit of %d in %d cases',
@@ -540,16 +463,15 @@ class _ComputeTGLRRun(_HipStepMixin):
             faint = _cache(orig).get('cube_faint')
             if faint is None:
                 faint = orig.cube_faint
-            areamap = getattr(orig.areamap, '_data', orig.areamap)
             if getattr(sess, 'host_mask', None) is None:
-                sess.host_mask = _host_mask(orig, faint.shape)
-            out = sess.tglr(faint, areamap, orig.PSF, orig.wfields, orig.profiles, size, pcut,
-                            pmeansub)
-            out['maxmap'], out['minmap'] = _HostImage(out['maxmap']), _HostImage(out['minmap'])
+                sess.host_mask = cubes.host_mask(orig.mask, faint.shape)
+            out = sess.tglr(faint, _data(orig.areamap), orig.PSF, orig.wfields, orig.profiles,
+                            size, pcut, pmeansub)
+            maxmap, minmap = out['maxmap'], out['minmap']
         else:
             ctx = _ctx_of(orig)
             _, _, mask = _inputs_on_device(orig, ctx)
-            faint = self._get_cube(orig, ctx, 'cube_faint')
+            faint = cubes.dense(ctx, session_cube(orig, 'cube_faint'))
             plan = kernels.GLRPlan(ctx, faint.shape, orig.PSF, orig.wfields, orig.profiles, pcut,
                                    pmeansub)
             try:
@@ -557,11 +479,12 @@ class _ComputeTGLRRun(_HipStepMixin):
                 ctx.sync()
             finally:
                 plan.close()
+            maxmap, minmap = out['maxmap'].to_host(), out['minmap'].to_host()
         self._put_cube(orig, 'cube_correl', out['correl'])
         self._put_cube(orig, 'cube_correl_min', out['correl_min'])
         self._put_cube(orig, 'cube_profile', out['profile'], np.uint8)
-        self.store_image('maxmap', out['maxmap'].to_host().astype(np.float64))
-        self.store_image('minmap', out['minmap'].to_host().astype(np.float64))
+        self.store_image('maxmap', maxmap.astype(np.float64))
+        self.store_image('minmap', minmap.astype(np.float64))
         self._put_cube(orig, 'cube_local_max', out['local_max'])
         self._put_cube(orig, 'cube_local_min', out['local_min'])
 
@@ -575,8 +498,6 @@ class _ComputePurityThresholdRun(_HipStepMixin):
 
     def run(self, orig, purity=0.9, purity_std=None, threshlist=None, pfasegfinal=1e-5,
             bins='fd'):
-        from .lib_origin import Compute_threshold_purity
-        ctx = _ctx_of(orig)
         if purity_std is None:
             purity_std = purity
         orig.param.update(dict(purity=purity, purity_std=purity_std))
@@ -587,16 +508,16 @@ class _ComputePurityThresholdRun(_HipStepMixin):
 
         self._loginfo('Estimation of threshold with purity = %.2f', purity)
         threshold, pval = Compute_threshold_purity(
-            purity, self._get_cube(orig, ctx, 'cube_local_max'),
-            self._get_cube(orig, ctx, 'cube_local_min'), segmap, threshlist=threshlist)
+            purity, session_cube(orig, 'cube_local_max'), session_cube(orig, 'cube_local_min'),
+            segmap, threshlist=threshlist)
         self.Pval = pval
         orig.param['threshold'] = threshold
         self._loginfo('Threshold: %.2f ', threshold)
 
         self._loginfo('Estimation of threshold std with purity = %.2f', purity_std)
         threshold_std, pval = Compute_threshold_purity(
-            purity_std, self._get_cube(orig, ctx, 'cube_std_local_max'),
-            self._get_cube(orig, ctx, 'cube_std_local_min'), threshlist=threshlist)
+            purity_std, session_cube(orig, 'cube_std_local_max'),
+            session_cube(orig, 'cube_std_local_min'), threshlist=threshlist)
         self.Pval_comp = pval
         orig.param['threshold_std'] = threshold_std
         self._loginfo('Threshold: %.2f ', threshold_std)
@@ -613,15 +534,12 @@ class _DetectionRun(_HipStepMixin):
 
     def det_correl_min(self, thresh=None):
         """3D positions of detections in correl_min (steps.py:935-939)."""
-        from . import detection
         orig = self.orig
         thresh = thresh or orig.param['threshold']
-        ctx = _ctx_of(orig)
-        return detection.det_correl_min(ctx, self._get_cube(orig, ctx, 'cube_local_min'), thresh)
+        return detection.det_correl_min(_ctx_of(orig), session_cube(orig, 'cube_local_min'), thresh)
 
     def run(self, orig, threshold=None, threshold_std=None, tol_spat=3, tol_spec=5,
             maxdist_lines=2.5, segmap=None):
-        from . import detection
         if threshold is not None:
             orig.threshold_correl = threshold
         if threshold_std is not None:
@@ -671,7 +589,6 @@ class _ComputeSpectraRun(_HipStepMixin):
     require = ('detection',)
 
     def run(self, orig, grid_dxy=0, spectrum_size_fwhm=6):
-        from . import lines
         cat2, line_est, line_var = lines.from_session(orig, orig.Cat1, grid_dxy)
         self.Cat2 = cat2
         self._loginfo('Save the updated catalog in self.Cat2 (%d lines)', len(cat2['z']))
@@ -703,7 +620,6 @@ class _CleanResultsRun(_HipStepMixin):
     require = ('compute_spectra',)
 
     def run(self, orig, merge_lines_z_threshold=5):
-        from . import catalog
         lines_, src, ts = catalog.from_session(
             orig, merge_lines_z_threshold=merge_lines_z_threshold)
         self.Cat3_lines = Catalog(lines_, {'CAT3_TS': ts})
@@ -716,26 +632,8 @@ class _CleanResultsRun(_HipStepMixin):
             self._loginfo('%d lines were merged in nearby lines', nb_line_merged)
 
 
-def _data(img):
-    """ndarray of an image attribute (mpdaf Image under the reference, ndarray here)."""
-    return np.asarray(getattr(img, '_data', img))
-
-
-class _HostImage:
-    """A map that is already on the host, where the run bodies expect ``.to_host()``."""
-
-    def __init__(self, arr):
-        self._a = np.asarray(arr)
-
-    def to_host(self):
-        return self._a
-
-
-def _host_mask(orig, shape):
-    m = orig.mask
-    if m is None or m is np.ma.nomask:
-        return np.zeros(shape, np.uint8)
-    return np.asarray(getattr(m, '_data', m))
+# ndarray of an image attribute (mpdaf Image under the reference, ndarray here)
+_data = cubes.host_array
 
 
 def _glr_halo(orig, size=3):
@@ -969,9 +867,9 @@ class SimpleOrig:
     @property
     def shape(self):
         """(Nz, Ny, Nx) of the processed cube."""
-        if isinstance(self.cube_raw, LazyCube):      # (no host copy for a shape)
+        if hasattr(self.cube_raw, 'shape'):      # (no host copy for a shape: a LazyCube has one)
             return tuple(self.cube_raw.shape)
-        return tuple(getattr(self.cube_raw, '_data', self.cube_raw).shape)
+        return tuple(_data(self.cube_raw).shape)
 
     # the thresholds of step 6, overridden by step 7's keywords (origin.py:496-513)
     @property

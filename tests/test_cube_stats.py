@@ -196,26 +196,17 @@ def test_arguments_are_checked(ctx):
 def test_tiled_cube_std_on_two_contexts_of_one_card():
     """``TiledCube.std()`` over two contexts on one card: each rank reduces the spaxels it owns
     (an irregular border, windows that overlap, arrays larger than their windows and NaN outside
-    them), the host adds the triples; equal to the one-context ``cube_std`` of the gathered cube."""
+    them), the host adds the triples; equal to the one-context ``cube_std`` of the gathered cube.
+    The other three reductions of the same cube, with and without a keep map, against NumPy."""
+    from _cube_forms import tiled
     from origin_amd import catalog, kernels
-    from origin_amd.session import DeviceGroup, TiledCube
+    from origin_amd.session import DeviceGroup
     rng = np.random.default_rng(8)
     shape = (9, 10, 13)
     field = rng.normal(5.0, 2.0, shape).astype(np.float32)
-    yy, xx = np.indices(shape[1:])
-    owner = (xx + 2 * (yy % 2) >= 7).astype(int)
-    windows = [(0, 10, 0, 9), (0, 10, 5, 13)]
     g = DeviceGroup([0, 0])
     try:
-        parts = []
-        for r, (y0, y1, x0, x1) in enumerate(windows):
-            by, bx = 1 + r, 2 - r
-            arr = np.full((shape[0], (y1 - y0) + 3, (x1 - x0) + 4), np.nan, np.float32)
-            arr[:, by:by + y1 - y0, bx:bx + x1 - x0] = field[:, y0:y1, x0:x1]
-            owned = owner[y0:y1, x0:x1] == r
-            assert not owned.all() and owned.any()
-            parts.append((g.ctxs[r].to_device(arr), (by, bx), (y0, y1, x0, x1), owned))
-        cube = TiledCube(g, shape, np.float32, parts)
+        cube = tiled(g, field)
         assert np.array_equal(cube.to_host(), field)
         ctx = g.ctxs[0]
         want = kernels.cube_std(ctx, cube.gathered(ctx))
@@ -228,5 +219,22 @@ def test_tiled_cube_std_on_two_contexts_of_one_card():
         n, s1, s2 = cube.moments(0.5)
         rn, r1, r2, rabs = reference(field, 0.5)
         assert n == rn and abs(s1 - r1) <= RTOL * rabs and abs(s2 - r2) <= RTOL * r2
+        f64 = field.astype(np.float64)
+        yy, xx = np.indices(shape[1:])
+        keep = (yy + 2 * xx) % 3 != 0
+        thr = [5.0, 0.0, 7.5, -0.2, 1e9]
+        for kp in (None, keep):
+            kept = f64 if kp is None else f64 * kp
+            assert np.array_equal(cube.zmax_map(kp), kept.max(axis=0))
+            sel = f64 if kp is None else f64[:, kp]
+            counts = [np.count_nonzero(sel > t) for t in thr]
+            assert np.array_equal(cube.count_above(thr, kp), counts)
+        aux = (np.arange(field.size) % 251).astype(np.uint8).reshape(shape)
+        w = cube.where_above(9.0, aux=tiled(g, aux, outside=0))
+        z, y, x = np.where(f64 > 9.0)
+        assert z.size > 10
+        for k, want in (("z", z), ("y", y), ("x", x), ("value", f64[z, y, x]),
+                        ("aux", aux[z, y, x])):
+            assert np.array_equal(w[k], want), k
     finally:
         g.close()

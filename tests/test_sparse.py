@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from _cube_forms import as_sparse
 from oracle import cpu_ref
 from oracle import golden_cases as gc
 
@@ -37,7 +38,7 @@ def cubes(shape, seed, smooth=True):
 def test_sparse_pass_is_the_dense_pass(ctx, shape):
     """Lists -> dense (device and host) equal the dense kernel's cubes bit for bit; so do the
     reductions of steps 6 and 7 (counts with and without a keep map, negative thresholds, per-spaxel
-    maxima, np.where order with the gathered profile cube)."""
+    maxima, np.where order with the gathered profile cube) and step 9's moments / std."""
     from origin_amd import kernels, sparse
     a, b, mask = cubes(shape, sum(shape), smooth=shape[0] % 2 == 1)
     Nz, Ny, Nx = shape
@@ -67,6 +68,11 @@ def test_sparse_pass_is_the_dense_pass(ctx, shape):
             w2 = kernels.where_above(ctx, dense_d, t, aux=aux)
             for k in ("z", "y", "x", "value", "aux"):
                 assert np.array_equal(w1[k], w2[k]), (t, k)
+        dd = sp.dense()
+        for kp in (None, keep):
+            kd = None if kp is None else ctx.to_device(kp)
+            assert sp.moments(0.25, kp) == kernels.cube_moments(ctx, dd, 0.25, kd)
+        assert np.float64(sp.std()).tobytes() == np.float64(kernels.cube_std(ctx, dd)).tobytes()
 
 
 def test_sparse_local_max_golden_and_fallbacks(ctx):
@@ -111,8 +117,8 @@ def test_purity_golden_on_sparse_cubes(ctx, name):
     import origin_amd.lib_origin as hip
     g = np.load(os.path.join(gc.GOLDEN_DIR, "g8_purity.npz"))
     inp = gc.g8_inputs()
-    smax = _as_sparse(ctx, inp["lmax"].astype(np.float32))
-    smin = _as_sparse(ctx, inp["lmin"].astype(np.float32))
+    smax = as_sparse(ctx, inp["lmax"].astype(np.float32))
+    smin = as_sparse(ctx, inp["lmin"].astype(np.float32))
     segmap = None if name == "noseg" else inp["segmap"]
     tl = list(inp["threshlist"]) if name == "lst" else None
     with np.errstate(all="ignore"):
@@ -122,32 +128,6 @@ def test_purity_golden_on_sparse_cubes(ctx, name):
     for c in ("Tval_r", "Pval_r", "Det_m", "Det_M"):
         assert np.array_equal(np.asarray(res[c], float), np.asarray(g[f"{name}_{c}"], float),
                               equal_nan=True), c
-
-
-def _as_sparse(ctx, dense):
-    """A SparseCube holding exactly the non-zero voxels of a host cube (one segment per 64
-    entries): the consumers' side of the format, independent of the pass that fills it."""
-    from origin_amd import sparse
-    idx = np.flatnonzero(dense.reshape(-1)).astype(np.int64)
-    val = dense.reshape(-1)[idx]
-    cap = 64
-    nseg = max(1, -(-len(idx) // cap))
-
-    class B:
-        pass
-    b = B()
-    b.ctx, b.shape, b.nseg, b.seg_cap = ctx, dense.shape, nseg, cap
-    pi = np.zeros(nseg * cap, np.int64)
-    pv = np.zeros(nseg * cap, np.float32)
-    pi[:len(idx)], pv[:len(idx)] = idx, val
-    cnt = np.zeros(2 * nseg, np.int32)
-    full, rest = divmod(len(idx), cap)
-    cnt[:full] = cap
-    if rest:
-        cnt[full] = rest
-    b.idx, b.val = [ctx.to_device(pi), None], [ctx.to_device(pv), None]
-    b.counts = ctx.to_device(cnt)
-    return sparse.SparseCube(b, 0)
 
 
 def test_step_chain_keeps_sparse_local_maxima(ctx):
