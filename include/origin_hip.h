@@ -174,6 +174,16 @@ int origin_cube_ingest_planes(origin_ctx *ctx, const void *d_data_be, int bitpix
                               const void *d_stat_be, int bitpix_stat, int nplanes, long S,
                               float *d_raw, float *d_var, uint8_t *d_mask, double *d_white_sum,
                               int *d_white_cnt);
+/* The same with a DQ unit: `nplanes` planes of big-endian integers, BITPIX 8, 16 or 32, aligned to
+ * their element size (the 16-byte form: to four elements).  A voxel whose DQ element is not zero
+ * is masked as well:
+ *     m = !isfinite(d) || !isfinite(s) || dq != 0
+ * and everything after m is as above.  d_dq_be == NULL with bitpix_dq == 0: no DQ unit, which is
+ * origin_cube_ingest_planes. */
+int origin_cube_ingest_planes_dq(origin_ctx *ctx, const void *d_data_be, int bitpix_data,
+                                 const void *d_stat_be, int bitpix_stat, const void *d_dq_be,
+                                 int bitpix_dq, int nplanes, long S, float *d_raw, float *d_var,
+                                 uint8_t *d_mask, double *d_white_sum, int *d_white_cnt);
 /* The same from an open file (replaces the float64 host read of Cube(filename), origin.py:213):
  * pread at the byte offsets of the two data units into two pinned buffers, chunk by chunk a whole
  * number of planes, H2D copy then kernel, file reads overlapping both as in origin_fits_read_data.
@@ -183,6 +193,18 @@ int origin_cube_ingest_planes(origin_ctx *ctx, const void *d_data_be, int bitpix
 int origin_cube_read(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
                      int bitpix_stat, int Nz, long S, int planes_per_chunk, float *d_raw,
                      float *d_var, uint8_t *d_mask, double *d_white_sum, int *d_white_cnt);
+/* Rows [y0, y1) of every plane of a (Nz, Ny, Nx) cube file -- one rank's band of a field cut into
+ * bands of whole rows -- by the same loop: one pread per plane and unit at
+ * off + ((z * Ny + y0) * Nx) * width, the band's planes packed in the pinned buffer (DATA, STAT,
+ * DQ, each section 256-byte aligned), H2D copies, the kernel with S = (y1 - y0) * Nx.  The outputs
+ * are band-shaped: (Nz, y1 - y0, Nx) cubes, (y1 - y0, Nx) sums.  off_dq < 0: no DQ unit; otherwise
+ * its non-zero elements (bitpix_dq 8, 16 or 32) are masked as in origin_cube_ingest_planes_dq.
+ * planes_per_chunk == 0: as many planes as fit 64 MiB of the band's file bytes.  y0 = 0, y1 = Ny
+ * without DQ is origin_cube_read. */
+int origin_cube_read_rows(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
+                          int bitpix_stat, long off_dq, int bitpix_dq, int Nz, int Ny, int Nx,
+                          int y0, int y1, int planes_per_chunk, float *d_raw, float *d_var,
+                          uint8_t *d_mask, double *d_white_sum, int *d_white_cnt);
 
 /* ---- inter-GPU exchange (one process per GPU; RCCL over xGMI on the context's stream) ----
  * The reference has no multi-GPU path (its only parallelism is the joblib pool of

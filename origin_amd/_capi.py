@@ -52,6 +52,9 @@ SIGNATURES = {
     "origin_fits_read_data": [vp, i32, i32, i64, i32, vp],
     "origin_cube_ingest_planes": [vp, vp, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp],
     "origin_cube_read": [vp, i32, i64, i32, i64, i32, i32, i64, i32, vp, vp, vp, vp, vp],
+    "origin_cube_ingest_planes_dq": [vp, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp],
+    "origin_cube_read_rows": [vp, i32, i64, i32, i64, i32, i64, i32, i32, i32, i32, i32, i32, i32,
+                              vp, vp, vp, vp, vp],
     "origin_comm_unique_id": [vp],
     "origin_comm_create": [vp, vp, i32, i32, PP(vp)],
     "origin_comm_destroy": [vp],

@@ -5,7 +5,9 @@
 // float64 and masks the voxels where either is not finite; cube_raw / var / mask (origin.py:262-274)
 // are then data.filled(0), var.filled(inf) and the mask, and ima_white (origin.py:240) is the
 // masked mean over z.  Here the file's big-endian bytes are copied to HBM as they are, and one
-// kernel swaps, narrows, masks and fills them and adds the planes to the per-spaxel sums.
+// kernel swaps, narrows, masks and fills them and adds the planes to the per-spaxel sums.  The
+// planes may be whole or one rank's band of rows (origin_cube_read_rows), and a DQ unit, where
+// the caller gives one, masks the voxels whose element is not zero.
 //
 // Pure byte work, HBM bound: per voxel |BITPIX| / 8 bytes of each unit in, 4 + 4 + 1 bytes out;
 // the sums (8 + 4 bytes per spaxel) move once per launch, not once per plane.
@@ -52,13 +54,41 @@ __device__ __forceinline__ void load_be(const uint8_t *__restrict__ src, long e,
 
 __device__ __forceinline__ bool finite_bits(unsigned b) { return (b & 0x7f800000u) != 0x7f800000u; }
 
+// The DQ flags of N consecutive voxels from element index e on: f[i] != 0 where the element is
+// not zero.  That test needs no byte swap, so the big-endian bytes are looked at as they lie:
+// N == 4 reads the four elements with one 4- (BITPIX 8), 8- (16) or 16-byte (32) load.
+template <int BQ, int N>
+__device__ __forceinline__ void load_dq(const uint8_t *__restrict__ src, long e, unsigned (&f)[N]) {
+  if constexpr (N == 4) {
+    if constexpr (BQ == 8) {
+      const unsigned q = *(const unsigned *)(src + e);
+      f[0] = q & 0xffu, f[1] = q & 0xff00u, f[2] = q & 0xff0000u, f[3] = q & 0xff000000u;
+    } else if constexpr (BQ == 16) {
+      const uint2 q = *(const uint2 *)(src + e * 2);
+      f[0] = q.x & 0xffffu, f[1] = q.x & 0xffff0000u, f[2] = q.y & 0xffffu, f[3] = q.y & 0xffff0000u;
+    } else {
+      const uint4 q = *(const uint4 *)(src + e * 4);
+      f[0] = q.x, f[1] = q.y, f[2] = q.z, f[3] = q.w;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      if constexpr (BQ == 8) f[i] = src[e + i];
+      else if constexpr (BQ == 16) f[i] = ((const unsigned short *)src)[e + i];
+      else f[i] = ((const unsigned *)src)[e + i];
+    }
+  }
+}
+
 // A lane owns N consecutive voxels of a plane (N == 4: 16-byte loads and stores, one 4-byte mask
 // store; N == 1 where S % 4 != 0 or a base is not 16-byte aligned) and marches the chunk's planes
 // with the sums of its spaxels in registers: read once, one plane added after the other, written
 // once.  No other lane of the launch touches those spaxels, and launches are ordered on the stream.
-template <int BD, int BS, int N>
+// BQ: BITPIX of the DQ unit (8, 16, 32) whose non-zero elements are masked too; 0: no DQ unit.
+template <int BD, int BS, int BQ, int N>
 __global__ __launch_bounds__(64) void cube_ingest_kernel(
-    const uint8_t *__restrict__ data_be, const uint8_t *__restrict__ stat_be, int nplanes, long S,
+    const uint8_t *__restrict__ data_be, const uint8_t *__restrict__ stat_be,
+    const uint8_t *__restrict__ dq_be, int nplanes, long S,
     float *__restrict__ raw, float *__restrict__ var, uint8_t *__restrict__ mask,
     double *__restrict__ wsum, int *__restrict__ wcnt) {
   const long groups = S / N;
@@ -82,9 +112,13 @@ __global__ __launch_bounds__(64) void cube_ingest_kernel(
       unsigned d[N], v[N], m[N];
       load_be<BD, N>(data_be, e, d);
       load_be<BS, N>(stat_be, e, v);
+      if constexpr (BQ != 0) load_dq<BQ, N>(dq_be, e, m);
 #pragma unroll
       for (int i = 0; i < N; ++i) {
-        m[i] = !(finite_bits(d[i]) && finite_bits(v[i]));
+        if constexpr (BQ != 0)
+          m[i] = !(finite_bits(d[i]) && finite_bits(v[i])) || m[i] != 0;
+        else
+          m[i] = !(finite_bits(d[i]) && finite_bits(v[i]));
         d[i] = m[i] ? 0u : d[i];
         v[i] = m[i] ? 0x7f800000u : v[i];
         // (a masked voxel adds +0.0, as NumPy's sum of data.filled(0) does; a lone -0.0 too
@@ -116,17 +150,28 @@ __global__ __launch_bounds__(64) void cube_ingest_kernel(
   }
 }
 
-template <int BD, int BS>
-void launch_ingest(origin_ctx *ctx, bool vec, const uint8_t *d, const uint8_t *s, int nplanes, long S,
-                   float *raw, float *var, uint8_t *mask, double *wsum, int *wcnt) {
+template <int BD, int BS, int BQ>
+void launch_ingest(origin_ctx *ctx, bool vec, const uint8_t *d, const uint8_t *s, const uint8_t *q,
+                   int nplanes, long S, float *raw, float *var, uint8_t *mask, double *wsum,
+                   int *wcnt) {
   const long groups = vec ? S / 4 : S;
   const int grid = (int)std::min<long>((groups + 63) / 64, (long)ctx->num_cu * 32);
   if (vec)
-    hipLaunchKernelGGL((cube_ingest_kernel<BD, BS, 4>), dim3(grid), dim3(64), 0, ctx->stream, d, s,
-                       nplanes, S, raw, var, mask, wsum, wcnt);
+    hipLaunchKernelGGL((cube_ingest_kernel<BD, BS, BQ, 4>), dim3(grid), dim3(64), 0, ctx->stream, d,
+                       s, q, nplanes, S, raw, var, mask, wsum, wcnt);
   else
-    hipLaunchKernelGGL((cube_ingest_kernel<BD, BS, 1>), dim3(grid), dim3(64), 0, ctx->stream, d, s,
-                       nplanes, S, raw, var, mask, wsum, wcnt);
+    hipLaunchKernelGGL((cube_ingest_kernel<BD, BS, BQ, 1>), dim3(grid), dim3(64), 0, ctx->stream, d,
+                       s, q, nplanes, S, raw, var, mask, wsum, wcnt);
+}
+
+template <int BD, int BS, class... A>
+void launch_ingest_dq(int bitpix_dq, A... a) {
+  switch (bitpix_dq) {
+    case 0: return launch_ingest<BD, BS, 0>(a...);
+    case 8: return launch_ingest<BD, BS, 8>(a...);
+    case 16: return launch_ingest<BD, BS, 16>(a...);
+    default: return launch_ingest<BD, BS, 32>(a...);
+  }
 }
 
 bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -149,10 +194,10 @@ int pread_all(int fd, char *p, size_t bytes, off_t off) {
 
 extern "C" {
 
-int origin_cube_ingest_planes(origin_ctx *ctx, const void *d_data_be, int bitpix_data,
-                              const void *d_stat_be, int bitpix_stat, int nplanes, long S,
-                              float *d_raw, float *d_var, uint8_t *d_mask, double *d_white_sum,
-                              int *d_white_cnt) {
+int origin_cube_ingest_planes_dq(origin_ctx *ctx, const void *d_data_be, int bitpix_data,
+                                 const void *d_stat_be, int bitpix_stat, const void *d_dq_be,
+                                 int bitpix_dq, int nplanes, long S, float *d_raw, float *d_var,
+                                 uint8_t *d_mask, double *d_white_sum, int *d_white_cnt) {
   ORIGIN_USE(ctx);
   ORIGIN_CHECK_ARG(d_data_be && d_stat_be && d_raw && d_var && d_mask && d_white_sum && d_white_cnt,
                    "null pointer");
@@ -160,42 +205,62 @@ int origin_cube_ingest_planes(origin_ctx *ctx, const void *d_data_be, int bitpix
   ORIGIN_CHECK_ARG((bitpix_data == -32 || bitpix_data == -64) &&
                        (bitpix_stat == -32 || bitpix_stat == -64),
                    "BITPIX %d / %d: only -32 and -64 are ingested", bitpix_data, bitpix_stat);
+  ORIGIN_CHECK_ARG(d_dq_be ? (bitpix_dq == 8 || bitpix_dq == 16 || bitpix_dq == 32) : bitpix_dq == 0,
+                   "DQ BITPIX %d: 8, 16 or 32 with a DQ unit, 0 without one", bitpix_dq);
   ORIGIN_CHECK_ARG(aligned(d_data_be, 8) && aligned(d_stat_be, 8), "file bytes must be 8-byte aligned");
+  ORIGIN_CHECK_ARG(!d_dq_be || aligned(d_dq_be, bitpix_dq / 8),
+                   "DQ bytes must be aligned to their %d-byte elements", bitpix_dq / 8);
   ORIGIN_CHECK_ARG(aligned(d_raw, 4) && aligned(d_var, 4) && aligned(d_white_sum, 8) &&
                        aligned(d_white_cnt, 4),
                    "misaligned output");
+  // (the four DQ elements of a lane are one load of 4 * bitpix_dq / 8 bytes)
   const bool vec = S % 4 == 0 && aligned(d_data_be, 16) && aligned(d_stat_be, 16) &&
-                   aligned(d_raw, 16) && aligned(d_var, 16) && aligned(d_mask, 4) &&
-                   aligned(d_white_sum, 16) && aligned(d_white_cnt, 16);
-  const uint8_t *d = (const uint8_t *)d_data_be, *s = (const uint8_t *)d_stat_be;
+                   (!d_dq_be || aligned(d_dq_be, bitpix_dq / 2)) && aligned(d_raw, 16) &&
+                   aligned(d_var, 16) && aligned(d_mask, 4) && aligned(d_white_sum, 16) &&
+                   aligned(d_white_cnt, 16);
+  const uint8_t *d = (const uint8_t *)d_data_be, *s = (const uint8_t *)d_stat_be,
+                *q = (const uint8_t *)d_dq_be;
   if (bitpix_data == -32 && bitpix_stat == -32)
-    launch_ingest<-32, -32>(ctx, vec, d, s, nplanes, S, d_raw, d_var, d_mask, d_white_sum, d_white_cnt);
+    launch_ingest_dq<-32, -32>(bitpix_dq, ctx, vec, d, s, q, nplanes, S, d_raw, d_var, d_mask,
+                               d_white_sum, d_white_cnt);
   else if (bitpix_data == -32)
-    launch_ingest<-32, -64>(ctx, vec, d, s, nplanes, S, d_raw, d_var, d_mask, d_white_sum, d_white_cnt);
+    launch_ingest_dq<-32, -64>(bitpix_dq, ctx, vec, d, s, q, nplanes, S, d_raw, d_var, d_mask,
+                               d_white_sum, d_white_cnt);
   else if (bitpix_stat == -32)
-    launch_ingest<-64, -32>(ctx, vec, d, s, nplanes, S, d_raw, d_var, d_mask, d_white_sum, d_white_cnt);
+    launch_ingest_dq<-64, -32>(bitpix_dq, ctx, vec, d, s, q, nplanes, S, d_raw, d_var, d_mask,
+                               d_white_sum, d_white_cnt);
   else
-    launch_ingest<-64, -64>(ctx, vec, d, s, nplanes, S, d_raw, d_var, d_mask, d_white_sum, d_white_cnt);
+    launch_ingest_dq<-64, -64>(bitpix_dq, ctx, vec, d, s, q, nplanes, S, d_raw, d_var, d_mask,
+                               d_white_sum, d_white_cnt);
   ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }
 
-int origin_cube_read(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
-                     int bitpix_stat, int Nz, long S, int planes_per_chunk, float *d_raw,
-                     float *d_var, uint8_t *d_mask, double *d_white_sum, int *d_white_cnt) {
-  ORIGIN_USE(ctx);
-  ORIGIN_CHECK_ARG(fd >= 0 && off_data >= 0 && off_stat >= 0 && Nz > 0 && S > 0 &&
-                       planes_per_chunk >= 0,
-                   "bad arguments");
-  ORIGIN_CHECK_ARG((bitpix_data == -32 || bitpix_data == -64) &&
-                       (bitpix_stat == -32 || bitpix_stat == -64),
-                   "BITPIX %d / %d: only -32 and -64 are ingested", bitpix_data, bitpix_stat);
-  const long wd = -bitpix_data / 8, ws = -bitpix_stat / 8;
-  long ppc = planes_per_chunk ? planes_per_chunk : std::max(1l, IO_CHUNK_BYTES / (S * (wd + ws)));
+int origin_cube_ingest_planes(origin_ctx *ctx, const void *d_data_be, int bitpix_data,
+                              const void *d_stat_be, int bitpix_stat, int nplanes, long S,
+                              float *d_raw, float *d_var, uint8_t *d_mask, double *d_white_sum,
+                              int *d_white_cnt) {
+  return origin_cube_ingest_planes_dq(ctx, d_data_be, bitpix_data, d_stat_be, bitpix_stat, nullptr,
+                                      0, nplanes, S, d_raw, d_var, d_mask, d_white_sum,
+                                      d_white_cnt);
+}
+
+// The stream behind both readers: spaxels [first, first + S) of every plane of `plane` spaxels.
+// A band of whole rows is one contiguous byte range of a plane, and the whole plane one of the
+// unit, so a chunk of whole planes is one pread per unit and a chunk of bands one per plane and
+// unit; in the pinned buffer the chunk's planes lie packed: DATA, STAT, DQ (each 256-byte aligned).
+static int read_band(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
+                     int bitpix_stat, long off_dq, int bitpix_dq, int Nz, long plane, long first,
+                     long S, int planes_per_chunk, float *d_raw, float *d_var, uint8_t *d_mask,
+                     double *d_white_sum, int *d_white_cnt) {
+  const long w[3] = {-bitpix_data / 8, -bitpix_stat / 8, off_dq < 0 ? 0 : bitpix_dq / 8};
+  const long off[3] = {off_data, off_stat, off_dq};
+  long ppc = planes_per_chunk ? planes_per_chunk
+                              : std::max(1l, IO_CHUNK_BYTES / (S * (w[0] + w[1] + w[2])));
   ppc = std::min<long>(ppc, Nz);
-  // one buffer: the chunk's DATA planes, then (256-byte aligned) its STAT planes
-  const size_t stat_at = ((size_t)(ppc * S * wd) + 255) & ~(size_t)255;
-  const size_t buf = (stat_at + (size_t)(ppc * S * ws) + 255) & ~(size_t)255;
+  size_t at[4] = {0, 0, 0, 0};
+  for (int u = 0; u < 3; ++u) at[u + 1] = (at[u] + (size_t)(ppc * S * w[u]) + 255) & ~(size_t)255;
+  const size_t buf = at[3];
   void *scr = nullptr;
   int rc = origin_scratch(ctx, 2 * buf, &scr);
   if (rc) return rc;
@@ -209,20 +274,31 @@ int origin_cube_read(origin_ctx *ctx, int fd, long off_data, int bitpix_data, lo
   const long nchunks = (Nz + ppc - 1) / ppc;
   for (long k = 0; k < nchunks; ++k) {
     const long z0 = k * ppc, np = std::min(ppc, Nz - z0);
-    const size_t nd = (size_t)(np * S * wd), ns = (size_t)(np * S * ws);
     char *h = (char *)st.h[k & 1], *d = (char *)scr + (k & 1) * buf;
     if (k >= 2) ORIGIN_HIP(hipEventSynchronize(st.ev[k & 1]));  // buffer free again
-    if ((rc = pread_all(fd, h, nd, (off_t)(off_data + z0 * S * wd))) ||
-        (rc = pread_all(fd, h + stat_at, ns, (off_t)(off_stat + z0 * S * ws)))) {
+    for (int u = 0; u < 3 && !rc; ++u) {
+      if (!w[u]) continue;
+      if (S == plane) {
+        rc = pread_all(fd, h + at[u], (size_t)(np * S * w[u]), (off_t)(off[u] + z0 * S * w[u]));
+      } else {
+        for (long z = z0; z < z0 + np && !rc; ++z)
+          rc = pread_all(fd, h + at[u] + (size_t)((z - z0) * S * w[u]), (size_t)(S * w[u]),
+                         (off_t)(off[u] + (z * plane + first) * w[u]));
+      }
+    }
+    if (rc) {
       (void)hipStreamSynchronize(ctx->stream);
       return rc;
     }
-    ORIGIN_HIP(hipMemcpyAsync(d, h, nd, hipMemcpyHostToDevice, ctx->stream));
-    ORIGIN_HIP(hipMemcpyAsync(d + stat_at, h + stat_at, ns, hipMemcpyHostToDevice, ctx->stream));
+    for (int u = 0; u < 3; ++u)
+      if (w[u])
+        ORIGIN_HIP(hipMemcpyAsync(d + at[u], h + at[u], (size_t)(np * S * w[u]),
+                                  hipMemcpyHostToDevice, ctx->stream));
     ORIGIN_HIP(hipEventRecord(st.ev[k & 1], ctx->stream));
-    rc = origin_cube_ingest_planes(ctx, d, bitpix_data, d + stat_at, bitpix_stat, (int)np, S,
-                                   d_raw + z0 * S, d_var + z0 * S, d_mask + z0 * S, d_white_sum,
-                                   d_white_cnt);
+    rc = origin_cube_ingest_planes_dq(ctx, d, bitpix_data, d + at[1], bitpix_stat,
+                                      w[2] ? d + at[2] : nullptr, w[2] ? bitpix_dq : 0, (int)np, S,
+                                      d_raw + z0 * S, d_var + z0 * S, d_mask + z0 * S, d_white_sum,
+                                      d_white_cnt);
     if (rc) {
       (void)hipStreamSynchronize(ctx->stream);
       return rc;
@@ -230,6 +306,40 @@ int origin_cube_read(origin_ctx *ctx, int fd, long off_data, int bitpix_data, lo
   }
   ORIGIN_HIP(hipStreamSynchronize(ctx->stream));
   return ORIGIN_OK;
+}
+
+int origin_cube_read(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
+                     int bitpix_stat, int Nz, long S, int planes_per_chunk, float *d_raw,
+                     float *d_var, uint8_t *d_mask, double *d_white_sum, int *d_white_cnt) {
+  ORIGIN_USE(ctx);
+  ORIGIN_CHECK_ARG(fd >= 0 && off_data >= 0 && off_stat >= 0 && Nz > 0 && S > 0 &&
+                       planes_per_chunk >= 0,
+                   "bad arguments");
+  ORIGIN_CHECK_ARG((bitpix_data == -32 || bitpix_data == -64) &&
+                       (bitpix_stat == -32 || bitpix_stat == -64),
+                   "BITPIX %d / %d: only -32 and -64 are ingested", bitpix_data, bitpix_stat);
+  return read_band(ctx, fd, off_data, bitpix_data, off_stat, bitpix_stat, -1, 0, Nz, S, 0, S,
+                   planes_per_chunk, d_raw, d_var, d_mask, d_white_sum, d_white_cnt);
+}
+
+int origin_cube_read_rows(origin_ctx *ctx, int fd, long off_data, int bitpix_data, long off_stat,
+                          int bitpix_stat, long off_dq, int bitpix_dq, int Nz, int Ny, int Nx,
+                          int y0, int y1, int planes_per_chunk, float *d_raw, float *d_var,
+                          uint8_t *d_mask, double *d_white_sum, int *d_white_cnt) {
+  ORIGIN_USE(ctx);
+  ORIGIN_CHECK_ARG(fd >= 0 && off_data >= 0 && off_stat >= 0 && planes_per_chunk >= 0,
+                   "bad arguments");
+  ORIGIN_CHECK_ARG(d_raw && d_var && d_mask && d_white_sum && d_white_cnt, "null pointer");
+  ORIGIN_CHECK_ARG(Nz > 0 && Ny > 0 && Nx > 0 && 0 <= y0 && y0 < y1 && y1 <= Ny,
+                   "bad shape: rows [%d, %d) of a %d x %d x %d cube", y0, y1, Nz, Ny, Nx);
+  ORIGIN_CHECK_ARG((bitpix_data == -32 || bitpix_data == -64) &&
+                       (bitpix_stat == -32 || bitpix_stat == -64),
+                   "BITPIX %d / %d: only -32 and -64 are ingested", bitpix_data, bitpix_stat);
+  ORIGIN_CHECK_ARG(off_dq < 0 || bitpix_dq == 8 || bitpix_dq == 16 || bitpix_dq == 32,
+                   "DQ BITPIX %d: only 8, 16 and 32 are read", bitpix_dq);
+  return read_band(ctx, fd, off_data, bitpix_data, off_stat, bitpix_stat, off_dq, bitpix_dq, Nz,
+                   (long)Ny * Nx, (long)y0 * Nx, (long)(y1 - y0) * Nx, planes_per_chunk, d_raw,
+                   d_var, d_mask, d_white_sum, d_white_cnt);
 }
 
 }  // extern "C"

@@ -339,10 +339,11 @@ _SPATIAL_CARD = re.compile(r"^(C(TYPE|UNIT|RPIX|RVAL|DELT|ROTA)[12]|(CD|PC)[12]_
 _SPECTRAL_CARD = re.compile(r"^(C(TYPE|UNIT|RPIX|RVAL|DELT)3|(CD|PC)(3_[123]|[12]_3))$")
 
 CubeFile = namedtuple("CubeFile", "path shape off_data bitpix_data off_stat bitpix_stat "
-                                  "wcs_header wave_header primary_header")
+                                  "wcs_header wave_header primary_header off_dq bitpix_dq",
+                      defaults=(None, None))
 
 
-def open_cube(path):
+def open_cube(path, dq=False):
     """The layout of a cube file, checked before any device call: a ``CubeFile`` with the shape
     ``(Nz, Ny, Nx)``, the byte offsets and BITPIX of the DATA and STAT data units, the spatial
     (``wcs_header``) and spectral (``wave_header``) world-coordinate cards of the DATA header as
@@ -350,9 +351,14 @@ def open_cube(path):
 
     DATA and STAT are found by EXTNAME, in either order; both must be 3-D IMAGE extensions of the
     same shape, BITPIX -32 or -64, without BSCALE / BZERO, and wholly in the file: anything else
-    is a ``ValueError`` naming the file and the reason.  A DQ extension is *ignored*, with a
-    warning: mpdaf would mask the voxels it flags, here the mask is the non-finite voxels of DATA
-    and STAT alone (what a MUSE pipeline cube carries: its DQ is folded into NaNs)."""
+    is a ``ValueError`` naming the file and the reason.  By default a DQ extension is *ignored*,
+    with a warning: mpdaf would mask the voxels it flags, here the mask is the non-finite voxels of
+    DATA and STAT alone (what a MUSE pipeline cube carries: its DQ is folded into NaNs).
+
+    ``dq=True`` takes the DQ extension in: ``off_dq`` / ``bitpix_dq`` of the result are its byte
+    offset and BITPIX (both ``None`` when the file has none), and the readers mask the voxels
+    whose DQ element is not zero.  It must be an IMAGE extension of DATA's shape, BITPIX 8, 16 or
+    32, without BSCALE / BZERO, and wholly in the file; anything else is refused in the same way."""
     try:
         hdus = scan(path)
     except ValueError as e:
@@ -365,7 +371,7 @@ def open_cube(path):
     for name in ("DATA", "STAT"):
         if name not in found:
             raise ValueError(f"{path}: no {name} image extension")
-    if "DQ" in found:
+    if "DQ" in found and not dq:
         logging.getLogger(__name__).warning(
             "%s: the DQ extension is ignored (only non-finite DATA / STAT voxels are masked)", path)
     size = os.path.getsize(path)
@@ -386,23 +392,68 @@ def open_cube(path):
         raise ValueError(f"{path}: DATA is {shapes['DATA']} but STAT is {shapes['STAT']}")
     if 0 in shapes["DATA"]:
         raise ValueError(f"{path}: empty cube {shapes['DATA']}")
+    off_dq = bitpix_dq = None
+    if dq and "DQ" in found:
+        hdr, off_dq, nb = found["DQ"]
+        bitpix_dq = hdr["BITPIX"]
+        shape = tuple(int(hdr[f"NAXIS{i}"]) for i in range(hdr.get("NAXIS", 0), 0, -1))
+        if shape != shapes["DATA"]:
+            raise ValueError(f"{path}: DATA is {shapes['DATA']} but DQ is {shape}")
+        if bitpix_dq not in (8, 16, 32):
+            raise ValueError(f"{path}: DQ has BITPIX = {bitpix_dq}, only 8, 16 and 32 are read")
+        if hdr.get("BSCALE", 1) != 1 or hdr.get("BZERO", 0) != 0:
+            raise ValueError(f"{path}: DQ is scaled (BSCALE / BZERO), which is not supported")
+        if size < off_dq + nb:
+            raise ValueError(f"{path}: the DQ data unit is truncated "
+                             f"({off_dq + nb - size} bytes missing)")
     hdr = found["DATA"][0]
     wcs = OrderedDict((k, v) for k, v in hdr.items() if _SPATIAL_CARD.match(k))
     wave = OrderedDict((k, v) for k, v in hdr.items() if _SPECTRAL_CARD.match(k))
     return CubeFile(path, shapes["DATA"], found["DATA"][1], hdr["BITPIX"], found["STAT"][1],
-                    found["STAT"][0]["BITPIX"], wcs, wave, hdus[0][0])
+                    found["STAT"][0]["BITPIX"], wcs, wave, hdus[0][0], off_dq, bitpix_dq)
 
 
-def read_cube(path, ctx=None, planes_per_chunk=0):
+def read_rows(info, ctx, rows, planes_per_chunk=0):
+    """Rows ``[y0, y1)`` of the cube file ``info`` (an ``open_cube`` result) on ``ctx``: the
+    band-shaped device arrays ``raw``, ``var``, ``mask`` and the host ``(sum, count)`` of the
+    band's white image (``origin_cube_read_rows``).  A DQ unit that ``info`` carries is applied."""
+    Nz, Ny, Nx = info.shape
+    y0, y1 = (int(v) for v in rows)
+    if not 0 <= y0 < y1 <= Ny:
+        raise ValueError(f"{info.path}: rows [{y0}, {y1}) of a cube with {Ny} rows")
+    shape = (Nz, y1 - y0, Nx)
+    raw, var = DeviceArray(ctx, shape, np.float32), DeviceArray(ctx, shape, np.float32)
+    mask = DeviceArray(ctx, shape, np.uint8)
+    wsum, wcnt = DeviceArray(ctx, shape[1:], np.float64), DeviceArray(ctx, shape[1:], np.int32)
+    no_dq = info.off_dq is None
+    with open(info.path, "rb", buffering=0) as f:
+        _capi.call("origin_cube_read_rows", ctx.handle, f.fileno(), info.off_data, info.bitpix_data,
+                   info.off_stat, info.bitpix_stat, -1 if no_dq else info.off_dq,
+                   0 if no_dq else info.bitpix_dq, Nz, Ny, Nx, y0, y1, int(planes_per_chunk),
+                   raw.p, var.p, mask.p, wsum.p, wcnt.p)
+    sums = wsum.to_host(), wcnt.to_host()
+    wsum.free()
+    wcnt.free()
+    return raw, var, mask, sums
+
+
+def read_cube(path, ctx=None, planes_per_chunk=0, rows=None, dq=False):
     """``(raw, var, mask, ima_white, wcs_header, wave_header)`` of a cube file: the float32 /
     float32 / uint8 device arrays as ``ORIGIN.init`` leaves cube_raw, var and mask (0 / inf / 1 at
     the voxels where DATA or STAT is not finite as float32, origin.py:262-274), the white image
     on the host (float64 mean over the unmasked voxels of each spaxel, NaN where there is none;
     origin.py:240) and the two card mappings of ``open_cube``.  The file bytes go to HBM as they
-    are, in chunks of ``planes_per_chunk`` planes (0: 64 MiB), and one kernel does the rest."""
-    info = open_cube(path)
+    are, in chunks of ``planes_per_chunk`` planes (0: 64 MiB), and one kernel does the rest.
+
+    ``rows=(y0, y1)``: only those rows of every plane are read; the arrays and the white image
+    are the band's, ``(Nz, y1 - y0, Nx)`` and ``(y1 - y0, Nx)``.  ``dq=True``: the voxels a DQ
+    extension flags (element != 0) are masked too (``open_cube``)."""
+    info = open_cube(path, dq=dq)
     ctx = ctx or default_context(0)
     Nz, Ny, Nx = info.shape
+    if rows is not None or info.off_dq is not None:
+        raw, var, mask, (wsum, wcnt) = read_rows(info, ctx, rows or (0, Ny), planes_per_chunk)
+        return raw, var, mask, white_image(wsum, wcnt), info.wcs_header, info.wave_header
     S = Ny * Nx
     raw, var = DeviceArray(ctx, info.shape, np.float32), DeviceArray(ctx, info.shape, np.float32)
     mask = DeviceArray(ctx, info.shape, np.uint8)
@@ -472,23 +523,24 @@ def read_host_image(path, ext=None):
 
 
 def write_cube(path, data, stat, header=None, bitpix=-32, primary_header=None, stat_first=False,
-               dq=None):
+               dq=None, dq_bitpix=32):
     """Write host arrays as a cube file -- ``<primary, no data> + DATA + STAT`` image extensions,
     mpdaf's layout -- with NumPy alone: for the synthetic fields, the tests and the timing tool.
     ``bitpix``: -32 / -64, or a pair (DATA, STAT).  ``header``: further cards of both extensions
     (the world coordinates); ``primary_header``: of the primary HDU.  ``stat_first`` swaps the two
-    extensions; ``dq``: an integer cube written as a third extension DQ (BITPIX 32)."""
+    extensions; ``dq``: an integer cube written as a third extension DQ (BITPIX ``dq_bitpix``:
+    8, 16 or 32)."""
     bd, bs = bitpix if isinstance(bitpix, (tuple, list)) else (bitpix, bitpix)
     units = [("DATA", np.asarray(data), bd), ("STAT", np.asarray(stat), bs)]
     if stat_first:
         units.reverse()
     if dq is not None:
-        units.append(("DQ", np.asarray(dq), 32))
+        units.append(("DQ", np.asarray(dq), dq_bitpix))
     tmp = path + ".part"
     with open(tmp, "wb") as f:
         f.write(header_bytes(_image_cards((), 8, True, extra=primary_header)))
         for name, arr, bp in units:
-            if bp not in (-32, -64, 32):
+            if bp not in ((8, 16, 32) if name == "DQ" else (-32, -64)):
                 raise ValueError(f"BITPIX {bp} is not written")
             f.write(header_bytes(_image_cards(arr.shape, bp, False, name,
                                               header if name != "DQ" else None)))

@@ -35,7 +35,7 @@ import threading
 
 import numpy as np
 
-from . import cubes, kernels, multigpu, pipeline, sparse
+from . import cubes, fitsio, kernels, multigpu, pipeline, sparse
 from .device import Context, DeviceArray, copy_box
 from .pca import GreedyPCA
 
@@ -364,28 +364,80 @@ class TiledSession:
                 np.ascontiguousarray(host[:, t.y0:t.y1, t.x0:t.x1]), dtype)
         self.group.run(one)
 
+    # -- step 0 --------------------------------------------------------------------
+    def open_cube(self, info, dq=False):
+        """Step 0 on the row bands of step 1: every rank's thread reads its own rows of the cube
+        file straight into its context (``fitsio.read_rows``: the band is one contiguous byte
+        range of every plane), so no rank and no host array ever holds the whole field.  ``info``:
+        the path of the file or its ``fitsio.open_cube`` result; ``dq``: mask what a DQ extension
+        flags.  Returns the TiledCubes raw, var, mask (float32 / float32 / uint8) and the white
+        image, stitched from the bands' sums."""
+        if isinstance(info, str):
+            info = fitsio.open_cube(info, dq=dq)
+        elif not dq:
+            info = info._replace(off_dq=None, bitpix_dq=None)
+        Nz, Ny, Nx = self.shape = tuple(info.shape)
+        # (the cuts of row_bands do not depend on the halo: preprocess() finds the same bands)
+        p1 = self.p1 = multigpu.OwnerTiling.row_bands(Ny, Nx, self.world, 1)
+        self.host_mask = None
+
+        def one(r):
+            t = p1.tile(r)
+            raw, var, mask, sums = fitsio.read_rows(info, self.group.ctxs[r], (t.y0, t.y1))
+            self.rk[r].update(raw=raw, var=var, mask=mask)
+            return sums
+        res = self.group.run(one)
+        white = fitsio.white_image(self._stitch_image(p1, [s for s, _ in res]),
+                                   self._stitch_image(p1, [c for _, c in res], np.int32))
+        return (self._cube("raw", np.float32, p1), self._cube("var", np.float32, p1),
+                self._cube("mask", np.uint8, p1), white)
+
+    def _own_bands(self, cube, name, p1):
+        """True where ``cube`` (or the ``LazyCube`` over it) is this session's TiledCube over the
+        per-rank arrays ``rk[r][name]`` on the bands of ``p1``: what ``open_cube`` left."""
+        cube = getattr(cube, "dev", cube)
+        if not (isinstance(cube, TiledCube) and cube.group is self.group):
+            return False
+        return all(name in st and cube.parts[r][0] is st[name]
+                   and tuple(cube.parts[r][2]) == (p1.tile(r).y0, p1.tile(r).y1, p1.tile(r).x0,
+                                                   p1.tile(r).x1)
+                   and tuple(st[name].shape) == (cube.shape[0],) + tuple(p1.tile_shape(r))
+                   for r, st in enumerate(self.rk))
+
     # -- step 1 --------------------------------------------------------------------
     def preprocess(self, raw, var, mask, dct_order=10, dct_approx=False, local_max_size=3):
         """``Preprocessing.run`` dense part (steps.py:431-465) on row bands.  raw / var / mask:
-        host arrays of the whole field.  Returns the TiledCubes cube_std, cont_dct,
-        cube_std_local_max / _min and the host images ima_std, ima_dct, o2 (O2 map of cube_std),
-        cont_o2 (mean_z cont_dct^2)."""
-        raw, var = cubes.host_array(raw), cubes.host_array(var)
-        Nz, Ny, Nx = raw.shape
-        mask = cubes.host_mask(mask, raw.shape)
-        self.shape, self.host_mask = (Nz, Ny, Nx), mask
+        host arrays of the whole field, or the TiledCubes of ``open_cube`` (as they are or under
+        their ``LazyCube``s): the bands then are where the file read left them and no host copy
+        of a cube is made.  Returns the TiledCubes cube_std, cont_dct, cube_std_local_max / _min
+        and the host images ima_std, ima_dct, o2 (O2 map of cube_std), cont_o2 (mean_z
+        cont_dct^2)."""
+        if not isinstance(getattr(raw, "dev", raw), TiledCube):
+            raw = cubes.host_array(raw)
+        Nz, Ny, Nx = tuple(raw.shape)
         halo = int(local_max_size) // 2
-        p1 = self.p1 = multigpu.OwnerTiling.row_bands(Ny, Nx, self.world, halo)
+        p1 = multigpu.OwnerTiling.row_bands(Ny, Nx, self.world, halo)
+        resident = all(self._own_bands(c, n, p1)
+                       for c, n in ((raw, "raw"), (var, "var"), (mask, "mask")))
+        if resident:
+            self.host_mask = None          # (step 5 gathers the uint8 mask when it needs it)
+        else:
+            raw, var = cubes.host_array(raw), cubes.host_array(var)
+            mask = self.host_mask = cubes.host_mask(mask, raw.shape)
+        self.shape, self.p1 = (Nz, Ny, Nx), p1
         self.group.attach()
 
         def one(r):
             ctx, comm, st = self.group.ctxs[r], self.group.comms[r], self.rk[r]
             t = p1.tile(r)
-            sl = (slice(None), slice(t.y0, t.y1), slice(t.x0, t.x1))
-            d_raw = ctx.to_device(np.ascontiguousarray(raw[sl]), np.float32)
-            d_var = ctx.to_device(np.ascontiguousarray(var[sl]), np.float32)
-            d_mask = ctx.to_device(np.ascontiguousarray(mask[sl]), np.uint8)
-            st.update(raw=d_raw, var=d_var, mask=d_mask)
+            if resident:
+                d_raw, d_var, d_mask = st["raw"], st["var"], st["mask"]
+            else:
+                sl = (slice(None), slice(t.y0, t.y1), slice(t.x0, t.x1))
+                d_raw = ctx.to_device(np.ascontiguousarray(raw[sl]), np.float32)
+                d_var = ctx.to_device(np.ascontiguousarray(var[sl]), np.float32)
+                d_mask = ctx.to_device(np.ascontiguousarray(mask[sl]), np.uint8)
+                st.update(raw=d_raw, var=d_var, mask=d_mask)
             how = (dict(allreduce_dev=comm.allreduce_sum_device) if comm.device_p2p
                    else dict(allreduce=comm.allreduce_sum))
             pre = pipeline.preprocess(ctx, d_raw, d_var, d_mask, dct_order, dct_approx, **how)

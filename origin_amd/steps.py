@@ -765,13 +765,15 @@ class SimpleOrig:
 
     @classmethod
     def from_cube(cls, cube, profiles, PSF, FWHM_PSF, LBDA_FWHM_PSF=None, wfields=None,
-                  FWHM_profiles=None, ctx=None, devices=None, backend=None, param=None):
+                  FWHM_profiles=None, ctx=None, devices=None, backend=None, param=None, dq=False):
         """Step 0 of the reference (``ORIGIN.__init__``, origin.py:210-244): a session from the
         path of a MUSE cube file.  The file's bytes go to HBM and one kernel leaves cube_raw, var
         and mask there (``fitsio.read_cube``); ``cube_raw`` / ``var`` / ``mask`` of the session
         are ``LazyCube``s over them (float64 / float64 / bool on demand, as the reference holds
         them), ``ima_white`` the masked mean over z, ``wcs_header`` / ``wave_header`` the world
-        coordinates of the DATA header, which ``Step.dump`` writes back.
+        coordinates of the DATA header, which ``Step.dump`` writes back.  ``dq=True`` also masks
+        the voxels a DQ extension flags (element != 0); by default the extension is ignored with
+        a warning.
 
         ``profiles``: the path of a dictionary (``fitsio.read_profiles``: fills ``FWHM_profiles``
         too) or a list of arrays.  ``PSF``: a ``(Nz, P, P)`` array or the path of its file, or a
@@ -779,9 +781,12 @@ class SimpleOrig:
         checked as origin.py:619-628.  ``FWHM_PSF``: in pixels, one per field.  Building the FSF
         from the ``FSF*`` keywords of the cube's header (``PSF=None`` in the reference) is
         mpdaf's ``FSFModel`` and is not here.  ``param['cubename']``, ``['profiles']`` and
-        ``['PSF']`` record the paths.  With ``devices`` the tiled session takes the host arrays
-        from the ``LazyCube``s, as it takes arrays."""
-        info = fitsio.open_cube(cube)
+        ``['PSF']`` record the paths.  With two or more ``devices`` every rank of the tiled
+        session reads the rows of its own band of step 1 from the file into its own context
+        (``TiledSession.open_cube``): the ``LazyCube``s then lie over ``TiledCube``s, step 1 runs
+        on the bands where they are, and the whole field is gathered only when somebody reads
+        ``._data`` or a later single-device step asks for it."""
+        info = fitsio.open_cube(cube, dq=dq)
         if PSF is None:
             raise ValueError(
                 "PSF=None: building the FSF from the FSF* keywords of the cube header is mpdaf's "
@@ -824,14 +829,20 @@ class SimpleOrig:
             PSF, wfields = check_psf(host(PSF)), None
             FWHM_PSF = float(np.mean(FWHM_PSF))
         ctx = ctx or default_context(0 if not devices else int(devices[0]))
-        raw, var, mask, ima_white, wcs, wave = fitsio.read_cube(cube, ctx)
-        orig = cls(LazyCube(raw), LazyCube(var), LazyCube(mask, dtype=bool), PSF, profiles,
-                   FWHM_PSF=FWHM_PSF, wfields=wfields, param=param, ctx=ctx, devices=devices,
-                   backend=backend, FWHM_profiles=FWHM_profiles)
+        orig = cls(None, None, None, PSF, profiles, FWHM_PSF=FWHM_PSF, wfields=wfields,
+                   param=param, ctx=ctx, devices=devices, backend=backend,
+                   FWHM_profiles=FWHM_profiles)
+        sess = _session_of(orig)
+        if sess is not None:               # every rank reads the rows of its band of step 1
+            raw, var, mask, ima_white = sess.open_cube(info, dq=dq)
+            wcs, wave = info.wcs_header, info.wave_header
+        else:
+            raw, var, mask, ima_white, wcs, wave = fitsio.read_cube(cube, ctx, dq=dq)
+            # where _inputs_on_device looks for them
+            _cache(orig).update(raw=raw, var=var, mask=mask)
+        orig.cube_raw, orig.var, orig.mask = LazyCube(raw), LazyCube(var), LazyCube(mask, dtype=bool)
         orig.LBDA_FWHM_PSF = LBDA_FWHM_PSF
         orig.ima_white, orig.wcs_header, orig.wave_header = ima_white, wcs, wave
-        if _session_of(orig) is None:      # where _inputs_on_device looks for them
-            _cache(orig).update(raw=raw, var=var, mask=mask)
         return orig
 
     def _bind(self, idx, cls):
