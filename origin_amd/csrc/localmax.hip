@@ -482,22 +482,38 @@ __global__ __launch_bounds__(256) void sparse_where_above_kernel(
   }
 }
 
-// map[s] = max(map[s], v) for the POSITIVE entries (the map starts at 0: every column of a
-// local-maximum cube holds zeros); positive floats order like their bit patterns
+// Floats as integers that order like them (negative floats: the magnitude bits flipped), and back.
+// A column of a local-maximum cube need not hold a zero (Nz == 1, a plateau of a negative
+// constant), so the entries alone do not give its maximum: the kernel keeps the maximum over the
+// kept entries of a column (keys; the map starts at the key of -inf) and counts them, and whoever
+// knows Nz lets the columns with fewer than Nz entries take their zeros (SparseCube.zmax_map).
+constexpr int LM_KEY_NEG_INF = (int)0x807fffffu;   // lm_key(-inf)
+__device__ __forceinline__ int lm_key(float v) {
+  const int b = __float_as_int(v);
+  return b >= 0 ? b : b ^ 0x7fffffff;
+}
+
 __global__ __launch_bounds__(256) void sparse_zmax_kernel(const long long *__restrict__ idx,
                                                           const float *__restrict__ val,
                                                           const int *__restrict__ counts,
                                                           int seg_cap, const uint8_t *__restrict__ keep,
-                                                          long S, int *__restrict__ map_bits) {
+                                                          long S, int *__restrict__ map_keys,
+                                                          int *__restrict__ col_entries) {
   const long seg = (long)blockIdx.x * seg_cap;
   const int n = min(counts[blockIdx.x], seg_cap);
   for (int i = threadIdx.x; i < n; i += 256) {
-    const float v = val[seg + i];
-    if (!(v > 0.0f)) continue;
     const long s_ = idx[seg + i] % S;
     if (keep && !keep[s_]) continue;
-    atomicMax(&map_bits[s_], __float_as_int(v));
+    atomicMax(&map_keys[s_], lm_key(val[seg + i]));
+    atomicAdd(&col_entries[s_], 1);
   }
+}
+
+__global__ __launch_bounds__(256) void sparse_zmax_decode_kernel(int *__restrict__ map_keys, long S) {
+  const long s = (long)blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  const int k = map_keys[s];
+  map_keys[s] = k >= 0 ? k : k ^ 0x7fffffff;   // (the flip is its own inverse)
 }
 
 struct LmGeom {
@@ -719,10 +735,16 @@ int origin_sparse_zmax_map(origin_ctx *ctx, const long long *d_idx, const float 
                            long S, float *d_map) {
   ORIGIN_USE(ctx);
   ORIGIN_CHECK_ARG(d_idx && d_val && d_counts && d_map && nseg > 0 && S > 0, "bad arguments");
-  ORIGIN_HIP(hipMemsetAsync(d_map, 0, (size_t)S * sizeof(float), ctx->stream));
+  // d_map [2 S]: S floats, the maximum over the kept entries of every column (-inf: none), then
+  // S ints, the number of those entries
+  int *keys = (int *)d_map, *entries = (int *)d_map + S;
+  ORIGIN_HIP(hipMemsetD32Async((hipDeviceptr_t)keys, LM_KEY_NEG_INF, (size_t)S, ctx->stream));
+  ORIGIN_HIP(hipMemsetAsync(entries, 0, (size_t)S * sizeof(int), ctx->stream));
   ProfScope ps(ctx, K_SMALL);
   hipLaunchKernelGGL(sparse_zmax_kernel, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, d_idx,
-                     d_val, d_counts, seg_cap, d_keep, S, (int *)d_map);
+                     d_val, d_counts, seg_cap, d_keep, S, keys, entries);
+  hipLaunchKernelGGL(sparse_zmax_decode_kernel, dim3((unsigned)cdiv(S, 256)), dim3(256), 0,
+                     ctx->stream, keys, S);
   ORIGIN_LAUNCH_CHECK();
   return ORIGIN_OK;
 }

@@ -178,28 +178,41 @@ class SparseCube(cubes.CubeForm):
         Nz, Ny, Nx = self.shape
         thr = np.ascontiguousarray(thresholds, dtype=np.float64)
         neg = thr < 0
-        if neg.any():   # the zeros of the dense cube are above a negative threshold too
-            thr = np.concatenate([thr, [-np.inf]])
-        out = np.zeros(thr.size, dtype=np.int64)
         kp, _hold = self._keep(keep)
-        _capi.call("origin_sparse_count_above", self.ctx.handle, *self._args(), kp, Ny * Nx,
-                   thr.size, thr.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
-        if neg.any():
-            kept = Ny * Nx if keep is None else int(np.count_nonzero(
-                keep.to_host() if isinstance(keep, DeviceArray) else np.asarray(keep)))
-            zeros = Nz * kept - int(out[-1])
-            out = out[:-1]
-            out[neg] += zeros
+
+        def count(t):
+            out = np.zeros(t.size, dtype=np.int64)
+            _capi.call("origin_sparse_count_above", self.ctx.handle, *self._args(), kp, Ny * Nx,
+                       t.size, t.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+            return out
+        if not neg.any():
+            return count(thr)
+        # the zeros of the dense cube are above a negative threshold too: all kept voxels less
+        # the kept entries (every entry is above -inf; counted in the same call while the list
+        # has room for one more threshold)
+        if thr.size < 1024:
+            out = count(np.concatenate([thr, [-np.inf]]))
+            out, entries = out[:-1], int(out[-1])
+        else:
+            out, entries = count(thr), int(count(np.array([-np.inf]))[0])
+        kept = Ny * Nx if keep is None else int(np.count_nonzero(
+            keep.to_host() if isinstance(keep, DeviceArray) else np.asarray(keep)))
+        out[neg] += Nz * kept - entries
         return out
 
     def zmax_map(self, keep=None):
-        """max over z per spaxel -> host float64 (Ny, Nx); keep == 0 spaxels give 0."""
+        """max over z per spaxel -> host float64 (Ny, Nx); keep == 0 spaxels give 0.  The device
+        returns the maximum over a column's kept entries (-inf: none) and their number; a column
+        with fewer than Nz entries holds a zero of the dense cube, which takes part here (a column
+        without one -- Nz == 1, a plateau of a negative constant -- keeps its negative maximum)."""
         self.counts()
         Nz, Ny, Nx = self.shape
-        m = self.ctx.empty((Ny, Nx), np.float32)
+        buf = self.ctx.empty((2, Ny, Nx), np.float32)
         kp, _hold = self._keep(keep)
-        _capi.call("origin_sparse_zmax_map", self.ctx.handle, *self._args(), kp, Ny * Nx, m.p)
-        return m.to_host().astype(np.float64)
+        _capi.call("origin_sparse_zmax_map", self.ctx.handle, *self._args(), kp, Ny * Nx, buf.p)
+        h = buf.to_host()
+        m, entries = h[0].astype(np.float64), h[1].view(np.int32)
+        return np.where(entries < Nz, np.maximum(m, 0.0), m)
 
     def moments(self, shift=0.0, keep=None):
         """kernels.cube_moments of the dense cube (its zeros are voxels like the others)."""

@@ -1,5 +1,6 @@
 """Cube forms built by hand, for the tests of their consumers (test_sparse.py, test_cube_stats.py,
-test_cube_forms.py): a ``SparseCube`` from a host cube and a ``TiledCube`` over two contexts."""
+test_cube_forms.py, test_hip_reduction_shapes.py): a ``SparseCube`` from a host cube (``as_sparse``:
+full segments; ``as_lists``: any counts, stale slots poisoned) and a ``TiledCube`` over two contexts."""
 import numpy as np
 
 # Two windows of a field at least 10 x 12 that overlap in x; ``owner`` cuts it along an irregular
@@ -30,6 +31,44 @@ def as_sparse(ctx, dense):
         cnt[full] = rest
     b.idx, b.val = [ctx.to_device(pi), None], [ctx.to_device(pv), None]
     b.counts = ctx.to_device(cnt)
+    return sparse.SparseCube(b, 0)
+
+
+POISON = np.float32(1e30)
+
+
+def as_lists(ctx, dense, seg_cap, counts, poison=True, seed=0):
+    """A SparseCube holding exactly the non-zero voxels of a host cube in ``len(counts)`` segments
+    of ``seg_cap`` slots, ``counts[s]`` entries in segment s (they add up to the non-zero voxels;
+    0 and ``seg_cap`` are allowed).  The entries are dealt to the segments in shuffled order.
+    ``poison``: every slot behind a segment's count holds a random index INSIDE the cube and the
+    value 1e30, so a consumer that read past ``min(counts, seg_cap)`` would show it in its result
+    without touching memory outside the arrays."""
+    from origin_amd import sparse
+    counts = np.asarray(counts, np.int32)
+    idx = np.flatnonzero(dense.reshape(-1)).astype(np.int64)
+    assert counts.ndim == 1 and counts.size >= 1 and counts.sum() == idx.size
+    assert counts.min() >= 0 and counts.max() <= seg_cap
+    rng = np.random.default_rng(seed)
+    idx = idx[rng.permutation(idx.size)]
+    nseg = counts.size
+    pi = np.zeros(nseg * seg_cap, np.int64)
+    pv = np.zeros(nseg * seg_cap, np.float32)
+    if poison:
+        pi[:] = rng.integers(0, dense.size, pi.size)
+        pv[:] = POISON
+    first = np.cumsum(counts) - counts                       # rank of a segment's first entry
+    seg = np.repeat(np.arange(nseg), counts)
+    slot = seg * seg_cap + (np.arange(idx.size) - first[seg])
+    pi[slot], pv[slot] = idx, dense.reshape(-1)[idx]
+
+    class B:
+        pass
+    b = B()
+    b.ctx, b.shape, b.nseg, b.seg_cap = ctx, dense.shape, nseg, int(seg_cap)
+    b.idx, b.val = [ctx.to_device(pi), None], [ctx.to_device(pv), None]
+    # (the second half belongs to the pass's other cube: full segments nobody may read as cube 0's)
+    b.counts = ctx.to_device(np.concatenate([counts, np.full(nseg, seg_cap, np.int32)]))
     return sparse.SparseCube(b, 0)
 
 
