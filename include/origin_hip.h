@@ -612,6 +612,39 @@ int origin_merge_detections(origin_ctx *ctx, long n, const int *h_x, const int *
                             const uint8_t *h_near, const uint8_t *h_far, int dzmax, int *h_comp,
                             int *h_area_out, int *h_imatch2, int *h_imatch);
 
+/* ---- G. segmentation maps ------------------------------------------------------------
+ * compute_segmap_gauss (lib_origin.py:243-280, called by Preprocessing.run, steps.py:473 and :481,
+ * and by ComputePurityThreshold.run, steps.py:862) behind its threshold fit, and the label of the
+ * union of two label maps (steps.py:487, :869): DESIGN.md section 3k.  Comparisons and integer
+ * work only; every result is bit-identical to the reference's.
+ *
+ * origin_segmap_mask: the mask of lib_origin.py:268-278 for a float64 device map (Ny, Nx):
+ *   stage 1  map > gamma, compared in float64 (NaN and -inf are 0)                        (:268)
+ *   stage 2  + binary_erosion, 4-neighbour cross, pixels outside the image count as 1     (:269)
+ *   stage 3  + binary_dilation, same cross, outside counts as 0                           (:270)
+ *   stage 4  + the disc of :273-278 when f >= 0: f = int(fwhm_fsf) // 2, a pixel is set where the
+ *            stage-3 mask has a pixel at an integer offset with dy^2 + dx^2 < f^2 (outside: 0).
+ *            That is fftconvolve(mask, disc, 'same') > 1e-9 evaluated directly: the convolution
+ *            is an integer count and the FFT's error is ~1e-15.  f = 0 gives the empty mask, f = 1
+ *            the identity; f is not capped.  f < 0: no disc (fwhm_fsf <= 0), the stage-3 mask.
+ * d_mask: uint8 [Ny*Nx], 0 / 1.  The stages below 4 exist for the unit tests.  Asynchronous.
+ * origin_segmap_union: d_mask[i] = d_a[i] > 0 || d_b[i] > 0 for two int32 label maps of n pixels
+ * (the argument of ndi.label at steps.py:487, :869).  Asynchronous.
+ * origin_segmap_label: scipy.ndimage.label(mask)[0] with the default 4-connected structure (:280):
+ * int32 labels 1..n in raster order of each component's first pixel, 0 for background; *h_n = n.
+ * Ny * Nx < 2^30.  No workgroup waits for another; the labels are the same from run to run.
+ * Synchronises. */
+int origin_segmap_mask(origin_ctx *ctx, const double *d_map, int Ny, int Nx, double gamma, int f,
+                       int stage, uint8_t *d_mask);
+int origin_segmap_union(origin_ctx *ctx, const int *d_a, const int *d_b, long n, uint8_t *d_mask);
+int origin_segmap_label(origin_ctx *ctx, const uint8_t *d_mask, int Ny, int Nx, int *d_labels,
+                        int *h_n);
+/* host-only geometry of the labeller: a workgroup builds the components of one tw x th tile; the
+ * roots of more than origin_label_scan_span() pixels are counted in more than one pass of the
+ * scan's one workgroup.  The tests derive their shapes from these. */
+int origin_label_tile(int *tw, int *th);
+int origin_label_scan_span(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,11 @@ SIGNATURES = {
                             vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "origin_merge_detections": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp,
                                 vp, vp],
+    "origin_label_tile": [PP(i32), PP(i32)],
+    "origin_label_scan_span": [],
+    "origin_segmap_mask": [vp, vp, i32, i32, C.c_double, i32, i32, vp],
+    "origin_segmap_union": [vp, vp, vp, i64, vp],
+    "origin_segmap_label": [vp, vp, i32, i32, vp, PP(i32)],
 }
 _RESTYPE = {"origin_last_error": C.c_char_p}
 

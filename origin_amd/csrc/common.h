@@ -46,6 +46,8 @@ enum OriginKernelId {
   K_MERGE_RENUMBER,  // seed ranks, group ids, the largest area of a group
   K_MERGE_STAGE2,    // z bitmaps and the cu / otg walk, one wave per area label
   K_STATS,           // moments of a cube (stats.hip): the streaming pass and its final wave
+  K_SEGMAP_MASK,     // segmentation maps (segmap.hip): threshold, erosion, dilation, disc, union
+  K_SEGMAP_LABEL,    // connected components: tiles, seams, flatten, scan, ranks, labels
   K_COUNT
 };
 
@@ -263,6 +265,33 @@ static inline int origin_use(origin_ctx *ctx) {
   } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// a[0..L) -> its exclusive prefix sums in place, a[L] = the total; ONE workgroup of THREADS,
+// thread t takes the chunk [t * per, (t + 1) * per) (merge.hip, segmap.hip)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void origin_scan_kernel(int L, int *a) {
+  __shared__ int part[THREADS];
+  const int t = threadIdx.x;
+  const int per = (L + THREADS - 1) / THREADS;
+  const int lo = min(L, t * per), hi = min(L, lo + per);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += a[i];
+  part[t] = s;
+  __syncthreads();
+  for (int off = 1; off < THREADS; off <<= 1) {
+    const int v = t >= off ? part[t - off] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int base = part[t] - s;
+  for (int i = lo; i < hi; ++i) {
+    const int v = a[i];
+    a[i] = base;
+    base += v;
+  }
+  if (t == THREADS - 1) a[L] = part[t];
+}
 
 // hipFuncSetAttribute (the dynamic-LDS ceiling of a kernel) holds per DEVICE, and a process may
 // drive several devices from several threads (origin_amd/session.py: one context and one thread

@@ -54,31 +54,6 @@ __global__ void hist_kernel(int n, const int *x, const int *y, int Nx, int *key,
   }
 }
 
-// a[0..L) -> its exclusive prefix sums in place, a[L] = the total; one workgroup
-__global__ __launch_bounds__(MG_SCAN) void scan_kernel(int L, int *a) {
-  __shared__ int part[MG_SCAN];
-  const int t = threadIdx.x;
-  const int per = (L + MG_SCAN - 1) / MG_SCAN;
-  const int lo = min(L, t * per), hi = min(L, lo + per);
-  int s = 0;
-  for (int i = lo; i < hi; ++i) s += a[i];
-  part[t] = s;
-  __syncthreads();
-  for (int off = 1; off < MG_SCAN; off <<= 1) {
-    const int v = t >= off ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int base = part[t] - s;
-  for (int i = lo; i < hi; ++i) {
-    const int v = a[i];
-    a[i] = base;
-    base += v;
-  }
-  if (t == MG_SCAN - 1) a[L] = part[t];
-}
-
 __global__ void scatter_kernel(int n, const int *key, int *cursor, int *binrows) {
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x)
     binrows[atomicAdd(&cursor[key[r]], 1)] = r;
@@ -409,7 +384,7 @@ struct MergeRun {
     ProfScope ps(ctx, K_MERGE_BIN);
     ORIGIN_HIP(hipMemsetAsync(start, 0, (size_t)(S + 1) * sizeof(int), ctx->stream));
     MG_LAUNCH(hist_kernel, gn, MG_BLOCK, 0, N, x, y, Nx, key, start);
-    MG_LAUNCH(scan_kernel, 1, MG_SCAN, 0, S, start);
+    MG_LAUNCH(origin_scan_kernel<MG_SCAN>, 1, MG_SCAN, 0, S, start);
     ORIGIN_HIP(hipMemcpyAsync(cursor, start, (size_t)(S + 1) * sizeof(int),
                               hipMemcpyDeviceToDevice, ctx->stream));
     MG_LAUNCH(scatter_kernel, gn, MG_BLOCK, 0, N, key, cursor, binrows);
@@ -466,7 +441,7 @@ struct MergeRun {
       ProfScope ps(ctx, K_MERGE_RENUMBER);
       ORIGIN_HIP(hipMemsetAsync(gid, 0xff, nb, ctx->stream));
       MG_LAUNCH(seed_flag_kernel, gn, MG_BLOCK, 0, N, imatch, rank);
-      MG_LAUNCH(scan_kernel, 1, MG_SCAN, 0, N, rank);
+      MG_LAUNCH(origin_scan_kernel<MG_SCAN>, 1, MG_SCAN, 0, N, rank);
       MG_LAUNCH(group_kernel<0>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
       MG_LAUNCH(group_kernel<1>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);
       MG_LAUNCH(group_kernel<2>, gn, MG_BLOCK, 0, N, imatch, rank, area, gid, garea, area_out);

@@ -549,3 +549,50 @@ def merge_detections(ctx, x0, y0, z0, area, shape, tol_spat, tol_spec):
                Nz, near.shape[0], _hp(near), _hp(far), int(np.ceil(tol_spec)) - 1, _hp(out["comp"]),
                _hp(out["area"]), _hp(out["imatch2"]), _hp(out["imatch"]))
     return out
+
+
+# ------------------------------------------------------------------------- segmentation maps
+def label_tile():
+    """(TW, TH): the tile one workgroup of ``origin_segmap_label`` builds the components of."""
+    tw, th = C.c_int(), C.c_int()
+    _capi.call("origin_label_tile", C.byref(tw), C.byref(th))
+    return tw.value, th.value
+
+
+def label_scan_span():
+    """Pixels whose root flags the labeller's one scan workgroup counts in a single pass."""
+    return _capi.load().origin_label_scan_span()
+
+
+def segmap_mask(ctx, data, gamma, f=-1, stage=4, out=None):
+    """``origin_segmap_mask``: the mask of ``compute_segmap_gauss`` (reference lib_origin.py:268-278)
+    of a float64 device map (Ny, Nx) -> uint8 DeviceArray.  ``f``: ``int(fwhm_fsf) // 2``, negative
+    = no disc; ``stage`` < 4 stops after the threshold (1), the erosion (2), the dilation (3)."""
+    if data.dtype != np.float64 or len(data.shape) != 2:
+        raise TypeError("segmap_mask needs a float64 device image")
+    Ny, Nx = data.shape
+    out = ctx.empty((Ny, Nx), np.uint8) if out is None else out
+    _capi.call("origin_segmap_mask", ctx.handle, data.p, Ny, Nx, float(gamma), int(f), int(stage),
+               out.p)
+    return out
+
+
+def segmap_union(ctx, a, b, out=None):
+    """``(a > 0) | (b > 0)`` of two int32 device label maps -> uint8 DeviceArray."""
+    if a.dtype != np.int32 or b.dtype != np.int32 or a.shape != b.shape:
+        raise TypeError("segmap_union needs two int32 device maps of one shape")
+    out = ctx.empty(a.shape, np.uint8) if out is None else out
+    _capi.call("origin_segmap_union", ctx.handle, a.p, b.p, a.size, out.p)
+    return out
+
+
+def segmap_label(ctx, mask, out=None):
+    """``scipy.ndimage.label(mask)`` (4-connected) of a uint8 device mask (Ny, Nx) ->
+    (int32 DeviceArray of labels, n)."""
+    if mask.dtype != np.uint8 or len(mask.shape) != 2:
+        raise TypeError("segmap_label needs a uint8 device image")
+    Ny, Nx = mask.shape
+    out = ctx.empty((Ny, Nx), np.int32) if out is None else out
+    n = C.c_int(0)
+    _capi.call("origin_segmap_label", ctx.handle, mask.p, Ny, Nx, out.p, C.byref(n))
+    return out, n.value

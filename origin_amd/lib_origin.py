@@ -17,13 +17,14 @@ import logging
 
 import numpy as np
 
-from . import catalog, cubes, detection, kernels, lines, sparse
+from . import catalog, cubes, detection, kernels, lines, segmap, sparse
 from .catalog import _columns
 from .device import default_context
 from .pca import GreedyPCA
 from .thresholds import compute_thresh_gaussfit
 
 __all__ = (
+    'compute_segmap_gauss',
     'dct_residual',
     'O2test',
     'Compute_PCA_threshold',
@@ -43,6 +44,12 @@ def _ctx():
 
 def _mask_on_device(ctx, mask, shape):
     return ctx.to_device(np.broadcast_to(cubes.host_mask(mask, shape), shape), np.uint8)
+
+
+def compute_segmap_gauss(data, pfa, fwhm_fsf=0, bins='fd'):
+    """gamma, labels (reference lib_origin.py:243-280): the threshold of the Gaussian fit on the
+    host, mask, erosion, dilation, disc and labels on the device (``origin_amd.segmap``)."""
+    return segmap.segmap_gauss(_ctx(), data, pfa, fwhm_fsf, bins=bins)
 
 
 def dct_residual(w_raw, order, var, approx, mask):

@@ -30,15 +30,12 @@ from datetime import datetime
 from enum import Enum
 
 import numpy as np
-from scipy import ndimage as ndi
-from scipy.signal import fftconvolve
 
-from . import catalog, cubes, detection, fitsio, kernels, lines, pipeline, sparse
+from . import catalog, cubes, detection, fitsio, kernels, lines, pipeline, segmap, sparse
 from .cubes import LazyCube, session_cube                         # noqa: F401 (LazyCube: re-export)
 from .cubes import cache as _cache, ctx_of as _ctx_of, inputs_on_device as _inputs_on_device
 from .device import default_context
 from .lib_origin import Compute_threshold_purity
-from .thresholds import compute_thresh_gaussfit
 
 __all__ = ('Preprocessing', 'CreateAreas', 'ComputePCAThreshold', 'ComputeGreedyPCA', 'ComputeTGLR',
            'ComputePurityThreshold', 'Detection', 'ComputeSpectra', 'CleanResults', 'Catalog',
@@ -267,22 +264,6 @@ class Step:
 
 
 # ----------------------------------------------------------------------------- helpers
-def compute_segmap_gauss(data, pfa, fwhm_fsf=0, bins='fd'):
-    """2-D host heuristic of reference lib_origin.py:243-280 (outside the hot path; kept so
-    that ``Preprocessing`` still fills ``segmap_cont`` / ``segmap_merged``)."""
-    histO2, frecO2, gamma, mea, std = compute_thresh_gaussfit(data, pfa, bins=bins)
-    mask = data > gamma
-    mask = ndi.binary_erosion(mask, border_value=1, iterations=1)
-    mask = ndi.binary_dilation(mask, iterations=1)
-    if fwhm_fsf > 0:
-        fwhm_pix = int(fwhm_fsf) // 2
-        size = fwhm_pix * 2 + 1
-        disc = np.hypot(*list(np.mgrid[:size, :size] - fwhm_pix)) < fwhm_pix
-        mask = fftconvolve(mask, disc, mode='same')
-        mask = mask > 1e-9
-    return gamma, ndi.label(mask)[0]
-
-
 # Devices of the sessions that do not say themselves (``register(devices=[...])`` sets it for
 # the reference's ORIGIN objects, which know nothing of GPUs); None = one context on device 0.
 _DEFAULT_DEVICES = None
@@ -362,14 +343,16 @@ class _PreprocessingRun(_HipStepMixin):
 
         mean_fwhm = int(np.ceil(np.mean(orig.FWHM_PSF)))
         self._loginfo('Segmentation based on the continuum')
+        # (mask, morphology and labels on the device, the several-device sessions included: the
+        # maps are whole images on the host here; the log10 stays NumPy's)
+        sctx = _ctx_of(orig)
         map1 = np.log10(cont_o2 * Nz)
-        thresh, map_cont = compute_segmap_gauss(map1, pfasegcont, mean_fwhm, bins=bins)
+        thresh, map_cont = segmap.segmap_gauss(sctx, map1, pfasegcont, mean_fwhm, bins=bins)
         self.store_image('segmap_cont', map_cont)
         self._loginfo('Segmentation based on the residual')
-        thresh, map_res = compute_segmap_gauss(o2, pfasegres, mean_fwhm, bins=bins)
+        thresh, map_res = segmap.segmap_gauss(sctx, o2, pfasegres, mean_fwhm, bins=bins)
         self._loginfo('Merging both maps')
-        segmap, nlabels = ndi.label((map_cont > 0) | (map_res > 0))
-        self.store_image('segmap_merged', segmap)
+        self.store_image('segmap_merged', segmap.merged_labels(sctx, map_cont, map_res))
 
 
 class _CreateAreasRun:
@@ -502,14 +485,15 @@ class _ComputePurityThresholdRun(_HipStepMixin):
             purity_std = purity
         orig.param.update(dict(purity=purity, purity_std=purity_std))
         # another segmap on the maxmap, merged with segmap_merged          (steps.py:862-867)
-        thresh, map_res = compute_segmap_gauss(_data(orig.maxmap), pfasegfinal, 0, bins=bins)
-        segmap, nlabels = ndi.label((map_res > 0) | (_data(orig.segmap_merged) > 0))
-        self.store_image('segmap_purity', segmap)
+        sctx = _ctx_of(orig)
+        thresh, map_res = segmap.segmap_gauss(sctx, _data(orig.maxmap), pfasegfinal, 0, bins=bins)
+        segmap_purity = segmap.merged_labels(sctx, map_res, _data(orig.segmap_merged))
+        self.store_image('segmap_purity', segmap_purity)
 
         self._loginfo('Estimation of threshold with purity = %.2f', purity)
         threshold, pval = Compute_threshold_purity(
             purity, session_cube(orig, 'cube_local_max'), session_cube(orig, 'cube_local_min'),
-            segmap, threshlist=threshlist)
+            segmap_purity, threshlist=threshlist)
         self.Pval = pval
         orig.param['threshold'] = threshold
         self._loginfo('Threshold: %.2f ', threshold)
