@@ -645,6 +645,33 @@ int origin_segmap_label(origin_ctx *ctx, const uint8_t *d_mask, int Ny, int Nx, 
 int origin_label_tile(int *tw, int *th);
 int origin_label_scan_span(void);
 
+/* ---- H. matching of point lists ------------------------------------------------------
+ * "Which points of A have a point of B within r, and the other way round" for two host tables:
+ * what the reference asks of two cKDTrees and query_ball_tree in compute_true_purity
+ * (lib_origin.py:2383-2399, once per threshold) and in Detection.run (steps.py:983-992): DESIGN.md
+ * section 3l.
+ *   h_ax, h_ay, h_az  float64 [n] host columns of A; h_bx, h_by, h_bz float64 [m] those of B;
+ *   r                 finite, >= 0;
+ *   h_aval            (may be NULL) float32 [n], a value per point of A, no NaN;
+ *   h_a_hit           (may be NULL) uint8 [n]: 1 where some B_j has d2(A_i, B_j) <= r*r;
+ *   h_b_hit           (may be NULL) uint8 [m]: the same, seen from B;
+ *   h_b_max           (may be NULL; needs h_aval) float32 [m]: the largest h_aval[i] over the A_i
+ *                     within r of B_j, -inf where there is none (-0 orders below +0).
+ * The predicate is part of the interface: with dx = ax - bx, dy = ay - by, dz = az - bz,
+ *   d2 = (dx*dx + dy*dy) + dz*dz <= r*r
+ * where every difference, product and sum is one separately rounded float64 operation in exactly
+ * this order (no fused multiply-add) and r*r is one rounded product made once on the host.  This
+ * is what NumPy computes for the same expression, so the outputs can be compared bit for bit.
+ * ORIGIN_E_ARG with a message for: a coordinate that is not finite, r negative or not finite,
+ * h_b_max without h_aval, a NaN in h_aval.  n == 0 or m == 0 launches nothing and fills the outputs
+ * (zeros, -inf).  The outputs do not depend on the order in which lanes arrive (integer atomicOr /
+ * atomicMax): they are the same from run to run, and a permutation of B's rows permutes h_b_hit /
+ * h_b_max and nothing else.  Synchronises. */
+int origin_ball_match(origin_ctx *ctx, long n, const double *h_ax, const double *h_ay,
+                      const double *h_az, const float *h_aval, long m, const double *h_bx,
+                      const double *h_by, const double *h_bz, double r, uint8_t *h_a_hit,
+                      uint8_t *h_b_hit, float *h_b_max);
+
 #ifdef __cplusplus
 }
 #endif

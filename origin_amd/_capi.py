@@ -120,6 +120,7 @@ SIGNATURES = {
                             vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "origin_merge_detections": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp,
                                 vp, vp],
+    "origin_ball_match": [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, C.c_double, vp, vp, vp],
     "origin_label_tile": [PP(i32), PP(i32)],
     "origin_label_scan_span": [],
     "origin_segmap_mask": [vp, vp, i32, i32, C.c_double, i32, i32, vp],

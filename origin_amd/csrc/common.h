@@ -48,6 +48,8 @@ enum OriginKernelId {
   K_STATS,           // moments of a cube (stats.hip): the streaming pass and its final wave
   K_SEGMAP_MASK,     // segmentation maps (segmap.hip): threshold, erosion, dilation, disc, union
   K_SEGMAP_LABEL,    // connected components: tiles, seams, flatten, scan, ranks, labels
+  K_MATCH_BIN,       // matching of point lists (match.hip): B binned into 3-D cells
+  K_MATCH_QUERY,     // every point of A against the cells around it
   K_COUNT
 };
 
@@ -267,7 +269,7 @@ static inline int origin_use(origin_ctx *ctx) {
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // a[0..L) -> its exclusive prefix sums in place, a[L] = the total; ONE workgroup of THREADS,
-// thread t takes the chunk [t * per, (t + 1) * per) (merge.hip, segmap.hip)
+// thread t takes the chunk [t * per, (t + 1) * per) (merge.hip, segmap.hip, match.hip)
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void origin_scan_kernel(int L, int *a) {
   __shared__ int part[THREADS];

@@ -209,7 +209,7 @@ static const char *kKernelNames[K_COUNT] = {
     "local_max",       "small",              "pca_total",
     "lines_gather",    "lines_uvec",         "lines_project",   "lines_ls",      "lines_select",
     "merge_bin",       "merge_components",   "merge_stage1",    "merge_renumber", "merge_stage2",
-    "cube_moments",    "segmap_mask",        "segmap_label"};
+    "cube_moments",    "segmap_mask",        "segmap_label",    "match_bin",     "match_query"};
 
 extern "C" {
 

@@ -17,7 +17,7 @@ Tables are plain dicts of NumPy columns (astropy is not a dependency of this pac
 """
 import numpy as np
 
-from . import cubes, kernels
+from . import cubes, kernels, match
 
 CAT0_COLUMNS = ("x0", "y0", "z0", "comp", "STD", "T_GLR", "profile")
 
@@ -38,6 +38,8 @@ def threshold_detections(ctx, cube_local_max, cube_profile, cube_std_local_max,
     rows, then std rows: the ``vstack`` of :981), ``cat_correl`` its correl rows and
     ``cat_std_kept`` the std rows farther than ``maxdist_lines`` from every correl detection
     (:983-994; in ascending row order) -- the two tables the reference stacks again at :1010.
+    The match of :983-992 runs on the device (``match.ball_match``); ``unmatched_std`` is the
+    host statement of the same rule.
     """
     c = cubes.where_above(cubes.resident(ctx, cube_local_max), threshold_correl,
                           aux=cubes.resident(ctx, cube_profile, np.uint8))
@@ -48,7 +50,10 @@ def threshold_detections(ctx, cube_local_max, cube_profile, cube_std_local_max,
     cat_std = dict(x0=s["x"], y0=s["y"], z0=s["z"], comp=np.ones(m, int), STD=s["value"],
                    T_GLR=np.full(m, np.nan), profile=np.zeros(m, np.uint8))
     cat0 = {k: np.concatenate([cat[k], cat_std[k]]) for k in CAT0_COLUMNS}
-    keep = unmatched_std(cat, cat_std, maxdist_lines)
+    hit = match.ball_match(ctx, (cat_std["x0"], cat_std["y0"], cat_std["z0"]),
+                           (cat["x0"], cat["y0"], cat["z0"]), maxdist_lines,
+                           want=("a_hit",))["a_hit"]
+    keep = np.flatnonzero(~hit)
     return cat0, cat, {k: v[keep] for k, v in cat_std.items()}
 
 

@@ -596,3 +596,38 @@ def segmap_label(ctx, mask, out=None):
     n = C.c_int(0)
     _capi.call("origin_segmap_label", ctx.handle, mask.p, Ny, Nx, out.p, C.byref(n))
     return out, n.value
+
+
+# ------------------------------------------------------------------------- matching of point lists
+def ball_match(ctx, a, b, r, a_val=None, want=None):
+    """``origin_ball_match``: points of ``a`` / ``b`` (three host columns x, y, z each) with a point
+    of the other list within ``r``, under the float64 predicate ``(dx*dx + dy*dy) + dz*dz <= r*r``
+    as NumPy rounds it (include/origin_hip.h).  Returns a dict with the outputs named in ``want``:
+    ``a_hit`` / ``b_hit`` (uint8, 0 / 1) and ``b_max`` (float32: the largest ``a_val`` within ``r``
+    of each point of ``b``, ``-inf`` where there is none).  ``want=None``: all that can be had,
+    ``b_max`` only with ``a_val``; the library refuses ``b_max`` asked for without it."""
+    A = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in a]
+    B = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in b]
+    if len(A) != 3 or len(B) != 3:
+        raise ValueError("a and b must have three columns (x, y, z) each")
+    n, m = A[0].size, B[0].size
+    if any(c.size != n for c in A) or any(c.size != m for c in B):
+        raise ValueError("the three columns of a list must have one length")
+    val = None
+    if a_val is not None:
+        val = np.ascontiguousarray(a_val, dtype=np.float32).reshape(-1)
+        if val.size != n:
+            raise ValueError("a_val must have one entry per point of a")
+    if want is None:
+        want = ("a_hit", "b_hit") + (("b_max",) if val is not None else ())
+    out = {}
+    if "a_hit" in want:
+        out["a_hit"] = np.zeros(n, np.uint8)
+    if "b_hit" in want:
+        out["b_hit"] = np.zeros(m, np.uint8)
+    if "b_max" in want:
+        out["b_max"] = np.zeros(m, np.float32)
+    _capi.call("origin_ball_match", ctx.handle, n, _hp(A[0]), _hp(A[1]), _hp(A[2]), _hp(val), m,
+               _hp(B[0]), _hp(B[1]), _hp(B[2]), float(r), _hp(out.get("a_hit")),
+               _hp(out.get("b_hit")), _hp(out.get("b_max")))
+    return out

@@ -17,7 +17,7 @@ import logging
 
 import numpy as np
 
-from . import catalog, cubes, detection, kernels, lines, segmap, sparse
+from . import catalog, cubes, detection, fitsio, kernels, lines, match, segmap, sparse
 from .catalog import _columns
 from .device import default_context
 from .pca import GreedyPCA
@@ -268,3 +268,65 @@ def add_tglr_stat(src_table, lines_table, correl, std):
     ctx = _ctx()
     return catalog.add_tglr_stat(_columns(src_table), lines_table,
                                  catalog.cube_std(ctx, correl), catalog.cube_std(ctx, std))
+
+
+# compute_true_purity: the reference's validation tool (it is called by hand, not by a step), so
+# it is not in __all__ either.  DESIGN.md section 3l.
+class _LinearWave:
+    """The linear spectral axis of a DATA header's cards: ``pixel`` as mpdaf's
+    ``WaveCoord.pixel`` gives it (0-based, not rounded)."""
+
+    def __init__(self, cards):
+        step = cards.get('CD3_3', cards.get('CDELT3'))
+        missing = [k for k, v in (('CRVAL3', cards.get('CRVAL3')), ('CRPIX3', cards.get('CRPIX3')),
+                                  ('CD3_3 or CDELT3', step)) if v is None]
+        if missing:
+            raise ValueError('the wave header lacks ' + ', '.join(missing))
+        self.crval, self.crpix = float(cards['CRVAL3']), float(cards['CRPIX3'])
+        self.step = float(step)
+
+    def pixel(self, lbda):
+        return (np.asarray(lbda, dtype=np.float64) - self.crval) / self.step + self.crpix - 1.0
+
+
+def _wave_axis(wave, cube):
+    for w in (wave, getattr(cube, 'wave', None)):
+        if w is None:
+            continue
+        return w if hasattr(w, 'pixel') else _LinearWave(w)
+    raise ValueError('no wave axis: give wave= (an object with .pixel(), or the CRVAL3 / CRPIX3 / '
+                     'CD3_3 cards of a session: wave=orig.wave_header), or a cube with a .wave')
+
+
+def compute_true_purity(cube_local_max, refcat, maxdist=4.5, threshmin=4, threshmax=7, plot=False,
+                        Pval=None, wave=None):
+    """True purity and completeness of a run against a catalogue of known lines (reference
+    lib_origin.py:2375-2443) through ``match.true_purity``: a dict of columns ``thresh, ndetect,
+    ntrue, nfalse, nmiss, purity``.
+
+    ``cube_local_max``: any form ``cubes.resident`` takes.  ``refcat``: the path of a FITS table
+    (read with ``fitsio.read_table``, not ``Table.read``) or a mapping of columns with ``TYPE``,
+    ``LOBS``, ``Q``, ``P``.  The lines are the rows with ``TYPE == 6``; the misses are counted
+    from ``nref = len(refcat)``, ALL rows -- a quirk of the reference (:2384, :2399) that is kept.
+    The z of a line is ``wave.pixel(LOBS)`` with ``wave`` the argument, else
+    ``cube_local_max.wave``; either is an object with ``.pixel()`` or the cards of a linear axis
+    (``CRVAL3``, ``CRPIX3``, ``CD3_3`` or ``CDELT3``: a session's ``orig.wave_header``, which the
+    caller passes as ``wave``).  ``ValueError`` names what is missing, before anything runs on
+    the device.  The reference's figure is not drawn: ``plot=True`` needs matplotlib as there
+    (``ImportError`` without it) and then raises ``NotImplementedError``, before anything runs;
+    the returned columns are what the figure shows.  ``Pval`` is accepted and not used."""
+    if plot:
+        import matplotlib  # noqa: F401
+        raise NotImplementedError('compute_true_purity draws no figure: plot the returned columns')
+    ref = _columns(fitsio.read_table(refcat) if isinstance(refcat, (str, bytes)) or
+                   hasattr(refcat, '__fspath__') else refcat)
+    missing = [k for k in ('TYPE', 'LOBS', 'Q', 'P') if k not in ref]
+    if missing:
+        raise ValueError('refcat lacks the column(s) ' + ', '.join(missing))
+    axis = _wave_axis(wave, cube_local_max)
+    lines6 = ref['TYPE'] == 6                                                   # :2381
+    zref = np.asarray(axis.pixel(ref['LOBS'][lines6]), dtype=np.float64)        # :2382
+    nref = len(ref['TYPE'])                                                     # :2384
+    tbl = match.true_purity(_ctx(), cube_local_max, (ref['Q'][lines6], ref['P'][lines6], zref),
+                            nref, maxdist, threshmin, threshmax)
+    return tbl
